@@ -2,6 +2,7 @@
 """bench.py — Msamples/s of the HIP path-tracing hot path (BASELINE.json metric).
 
     python bench.py [--gpus N --steps K --warmup W] [--config C2|C3|C4|C5]
+                    [--full] [--dump-outputs DIR]
     torchrun --nproc-per-node N bench.py --gpus N ...     (one rank per GPU)
 
 A step renders one full frame of the workload (every pixel x every stratum x up
@@ -11,7 +12,14 @@ xGMI brings the compact tile sums to rank 0; --shard strata splits the strata
 instead and combines full-frame sums with an RCCL reduce(sum).  Strong scaling:
 the frame is fixed, N varies.
 
-Output: ONE JSON line on rank 0 (driver contract) with
+A plain run (no --full) sets up, warms up, times the K steps, writes the last
+timed frame if --dump-outputs DIR is given (DIR/frame_sums.npy, see
+dump_outputs) and prints the line: the headline figure, ms_per_step, and the
+render kernel's roofline from its HIP-event time and the committed
+profiles/pmc_<config>.json.  Everything below that takes runs of its own is
+measured with --full only.
+
+Output: ONE JSON line on rank 0 (driver contract); with --full it carries
   * a roofline object for the render kernel: bound "valu" -- the kernel issues
     vector instructions most cycles and the scene is cache/LDS-resident, so the
     roof is the fp64 vector peak (78.6 TFLOP/s); achieved = fp64 FLOP per
@@ -621,6 +629,27 @@ def progressive_rates(torch, dev, width=1920, frames=30):
     return res
 
 
+DUMP_MAX_BYTES = 60 * 10 ** 6  # --dump-outputs: larger arrays are sampled down to this
+
+
+def dump_outputs(path, frame):
+    """--dump-outputs DIR: what the timed path handed its caller in the last
+    timed step -- the frame of raw radiance sums (RT_OUT_SUM: H x W x 3 fp64,
+    the image times spp) -- as DIR/frame_sums.npy.  The scene, the camera and
+    the per-step seeds are fixed by the arguments, so two builds run with the
+    same arguments write comparable files.  A frame above DUMP_MAX_BYTES (C5:
+    199 MB) is cut to a fixed sample of its pixels: the rows of the (H*W, 3)
+    view picked by numpy's default_rng(0), in ascending pixel order."""
+    import numpy as np
+    a = frame.detach().cpu().numpy()
+    if a.nbytes > DUMP_MAX_BYTES:
+        px = a.reshape(-1, a.shape[-1])
+        n = DUMP_MAX_BYTES // (px.shape[1] * px.itemsize)
+        a = px[np.sort(np.random.default_rng(0).choice(px.shape[0], size=n, replace=False))]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "frame_sums.npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def rank_diagnostics(torch, dist, dev, rank, ws, launch_work, exchange, wait_exchange, steps=2):
     """N>1: serial diagnostic steps after the timed region.  Each step: barrier,
     this rank's render timed with HIP events on its launch stream, then the
@@ -674,9 +703,19 @@ def main():
     ap.add_argument("--config", default="C2", choices=sorted(CONFIGS))
     ap.add_argument("--width", type=int, default=0)
     ap.add_argument("--spp", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="N=1: beside the headline figure, also the live rocprofv3 PMC passes, "
+                         "the kernel's STATS counters (cache-served bytes, lane utilisation), "
+                         "the other configs, the host-output and progressive rates and the CPU "
+                         "baseline; without it a run sets up, warms up, times the steps and "
+                         "prints the line (the roofline then from profiles/pmc_<config>.json)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the last timed step's frame of radiance "
+                         "sums to DIR/frame_sums.npy (fp64; sampled above 60 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full: skip the CPU baseline")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="N=1: skip timing C3 and C4 beside the headline config")
+                    help="--full: skip timing C3, C4 and C5 beside the headline config")
     # rehearsal of the N>1 path on one GPU: every rank on cuda:0, gloo all_reduce
     # instead of RCCL reduce (the driver's 8-GPU runs use the defaults)
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"])
@@ -703,10 +742,13 @@ def main():
     ap.add_argument("--fail-rank", type=int, default=-1, help=argparse.SUPPRESS)  # tests: that
     # rank exits 3 once the process group is up (the launcher must stop the others)
     ap.add_argument("--pmc", default="auto", choices=["auto", "file", "off"],
-                    help="N=1 roofline counters: auto = rocprofv3 PMC passes of this build "
-                         "run before the timed run (fallback: the committed "
-                         "profiles/pmc_<config>.json), file = the committed file only")
+                    help="N=1 roofline counters: auto = with --full, rocprofv3 PMC passes of "
+                         "this build run before the timed run (fallback, and without --full: "
+                         "the committed profiles/pmc_<config>.json), file = the committed "
+                         "file only")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     cpu = args.device == "cpu"
     if cpu and args.backend != "gloo":
         print("bench: --device cpu exchanges over gloo (--backend gloo)", file=sys.stderr)
@@ -721,10 +763,11 @@ def main():
               file=sys.stderr)
         sys.exit(2)
     pmc = None
-    full_line = (ws == 1 and not cpu and not args.no_other_configs and not args.width
-                 and not args.spp)
+    full_line = (args.full and ws == 1 and not cpu and not args.no_other_configs
+                 and not args.width and not args.spp)
     pmc_other = {}
-    if ws == 1 and args.pmc == "auto" and not cpu:  # before this process initialises the GPU
+    # the live passes run before this process initialises the GPU
+    if args.full and ws == 1 and args.pmc == "auto" and not cpu:
         pmc = pmc_live(args)
         if pmc and args.pmc_save:
             with open(args.pmc_save, "w") as fh:
@@ -895,6 +938,9 @@ def main():
         err = (last - ref).abs().max().item()
         scale = max(1.0, ref.abs().max().item())
         check = {"max_abs_diff": err, "ok": bool(err <= 1e-9 * scale)}
+    if args.dump_outputs and rank == 0:  # before anything below renders into the buffers again
+        assert final["step"] == args.steps - 1
+        dump_outputs(args.dump_outputs, final["frame"])
 
     diag = None
     if use_pg:  # kernel time measured after the timed region (no sync inside it)
@@ -909,6 +955,19 @@ def main():
 
     def gpu_roofline(pmc):
         # roofline of the dominant (render) kernel on this rank, one launch
+        avg_ms = sum(kernel_ms) / len(kernel_ms)
+        pmc = load_pmc(args, args.config, pmc) if ws == 1 else None
+        roof = roofline(pmc, avg_ms)
+        if args.full or ws > 1:
+            stats_figures(roof, avg_ms)
+        roof["note"] = ("fp64 vector roof (VALU-issue bound, scene LDS/cache resident); "
+                        "N>1 lines carry no PMC data (traffic null)"
+                        if ws == 1 else "N>1: no PMC pass in multi-rank runs (traffic null)")
+        return roof
+
+    def stats_figures(roof, avg_ms):
+        # the STATS instance's counters (a launch of its own): the cache-served
+        # bytes, the phase shares and the lane utilisation beside the roofline
         if tiles_mode:
             st = R.stats(frame, seed=0, tiles=(rank, ws), layout=abi.RT_LAYOUT_TILES,
                          chunks=shard.chunks)
@@ -916,10 +975,7 @@ def main():
             st = R.stats(frame, seed=0, samples=(s0, s1 - s0))
         px_launch = shard.tiles_per_rank * max(1, shard.chunks) * 64 if tiles_mode else W * H
         bytes_launch = algorithmic_bytes(st, info, px_launch)
-        avg_ms = sum(kernel_ms) / len(kernel_ms)
         achieved = bytes_launch / (avg_ms * 1e-3) / 1e9
-        pmc = load_pmc(args, args.config, pmc) if ws == 1 else None
-        roof = roofline(pmc, avg_ms)
         roof["cache_served"] = {"bytes_per_launch": int(bytes_launch),
                                 "bytes_per_sample": round(bytes_launch / max(1, st["samples"]), 1),
                                 "gbs": round(achieved, 1)}
@@ -948,10 +1004,6 @@ def main():
                 st["node_visits"] / (64 * st["model_trace_max"]), 4)
             roof["lane_utilisation"]["traversal_model_two_walks"] = round(
                 st["node_visits"] / (64 * max(1, st["model_trace_pair_max"])), 4)
-        roof["note"] = ("fp64 vector roof (VALU-issue bound, scene LDS/cache resident); "
-                        "N>1 lines carry no PMC data (traffic null)"
-                        if ws == 1 else "N>1: no PMC pass in multi-rank runs (traffic null)")
-        return roof
 
     if cpu:  # the CPU backend's ranks: no kernel, no roof
         roof = {"bound": None, "achieved": None, "peak": None, "unit": None, "frac": None,
@@ -1003,7 +1055,7 @@ def main():
         if not tiles_mode:
             out["host_output"] = host_output(torch, R, frame, max(3, min(args.steps, 10)))
         out["progressive"] = progressive_rates(torch, dev)
-    if rank == 0 and ws == 1 and not args.no_cpu_baseline:
+    if rank == 0 and ws == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(scene, cam)
     if rank == 0:
         print(json.dumps(out), flush=True)

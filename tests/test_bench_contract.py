@@ -46,11 +46,11 @@ def test_bench_line(layout):
 
 @pytest.mark.gpu
 def test_bench_line_live_pmc():
-    """Default --pmc auto: bench.py runs the rocprofv3 PMC passes (VALU, FETCH_SIZE,
+    """--full with the default --pmc auto: bench.py runs the rocprofv3 PMC passes (VALU, FETCH_SIZE,
     WRITE_SIZE) on this build before its timed run; the roofline is the fp64
     FLOP rate against the fp64 vector peak (<= 1), VALU-busy beside it, and
     traffic the PMC HBM bytes."""
-    d = _bench(timeout=400)
+    d = _bench("--full", timeout=400)
     rf = d["roofline"]
     assert rf["pmc_source"].startswith("live"), rf.get("pmc_source")
     assert 0 < rf["frac"] <= 1 and rf["traffic"] > 0 and 0 < rf["valu_busy"] <= 1
@@ -68,7 +68,7 @@ def test_bench_roofline_counts_issue_and_lanes(config):
     rate x SQ_THREAD_CYCLES_VALU / 64 SQ_ACTIVE_INST_VALU) sits beside frac,
     below it."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", config, "--steps", "2",
-           "--warmup", "1", "--no-cpu-baseline", "--no-other-configs"]
+           "--warmup", "1", "--full", "--no-cpu-baseline", "--no-other-configs"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=400)
     assert r.returncode == 0, r.stderr[-2000:]
     rf = json.loads(r.stdout.strip().splitlines()[-1])["roofline"]
