@@ -35,6 +35,12 @@
  *                        64-row batch into its rows of the frame, StaticCamera.cpp:281-299) for
  *                        tile shards: chunk partials summed and tiles reordered into frame rows
  *                        on the device, before the one copy out
+ *   rt_render_tiles_device / rt_adaptive_update_device / rt_adaptive_select_device /
+ *   rt_to_bytes_tiles_device
+ *                     <- no counterpart: DynamicCamera traces every stratum of every pixel
+ *                        (DynamicCamera.cpp:96-200); these stop sampling the 8x8 tiles whose
+ *                        estimate has converged (launches over a tile list, per-pixel moments,
+ *                        per-tile error, a display scale per tile)
  *   rt_last_error     <- replaces CUDA_CHECK's exit() and the converters' exceptions
  *                        (CudaMemoryUtility.cuh:9-15, HittableConverter.cuh:103-108): errors are
  *                        returned as negative codes, never thrown or exit()ed across the ABI.
@@ -462,6 +468,62 @@ int rt_last_kernel_ms(rt_scene *scene, double *ms);
    reference's write_color rule (ColorUtility.hpp:11-36). */
 int rt_to_bytes_device(const double *device_rgb, int64_t n_pixels, double scale,
                        uint8_t *device_bytes, void *hip_stream);
+
+/* ---- adaptive sampling (functions added under ABI 5: no struct or signature
+   above changed) ------------------------------------------------------------
+   Progressive accumulation that stops sampling the 8x8 tiles whose estimate
+   has converged (rtx/adaptive.py drives these; DESIGN.md "Adaptive sampling").
+   Tiles are numbered row-major over the row range / the frame, as
+   tile_first / tile_stride number them.  A tile list is device resident,
+   strictly ascending and in range -- the caller's contract; every entry is
+   clamped into [0, tiles - 1] on the device before use, so a bad list can
+   mis-render but never reaches memory outside the buffers described. */
+
+/* rt_render_device in RT_LAYOUT_FRAME restricted to the n_tiles tiles of
+   device_tiles: only their pixels are written (accumulate 0) or added to
+   (accumulate 1), every other pixel of device_rgb is left untouched.
+   params->tile_first / tile_stride / layout / strata_chunks must be
+   0 / 0-or-1 / RT_LAYOUT_FRAME / 0.  n_tiles 0 queues nothing; n_tiles above
+   the range's tile count is RT_ERR_INVALID.  The list is copied (a kernel on
+   hip_stream) into a scene-owned buffer, so work queued on hip_stream after
+   the call may rewrite it.  One stratum per launch gives each listed
+   pixel the value rt_render_device gives it bit for bit; more strata may be
+   split into other work units than the full frame's (rt_tuning's caveat:
+   agreement to rounding).  No dispatch order is measured or kept for a list. */
+int rt_render_tiles_device(rt_scene *scene, const rt_frame *frame, const rt_render_params *params,
+                           const int32_t *device_tiles, int32_t n_tiles, double *device_rgb,
+                           void *hip_stream);
+
+/* One batch of batch_strata strata per pixel, rendered as raw sums into
+   device_delta ([H][W][3]), folded into the state of the listed tiles -- one
+   wavefront per tile, one lane per pixel.  Per pixel: acc += delta; with
+   y = (0.2126 r + 0.7152 g + 0.0722 b of delta) / batch_strata: s1 += y,
+   s2 += y * y (s1, s2: [H][W]).  Per tile: tile_strata[t] += batch_strata
+   (tile_strata: [tiles of the frame]). */
+int rt_adaptive_update_device(const double *device_delta, int32_t batch_strata, const int32_t *device_tiles,
+                              int32_t n_tiles, const rt_frame *frame, double *device_acc, double *device_s1,
+                              double *device_s2, int32_t *device_tile_strata, void *hip_stream);
+
+/* The tiles of device_tiles_in that still need samples, in the same
+   (ascending) order, into device_tiles_out (room for n_in entries; must not
+   alias the input), their number into device_count_out[0].  For a tile with
+   b = tile_strata[t] / batch_strata batches, per pixel inside the image:
+   mean = s1 / b, var = max(0, (s2 - s1 * s1 / b) / (b - 1)),
+   se = sqrt(var / b); the tile's error e_t is the average of
+   se / (mean + floor) over those pixels (infinite while b < 2), stored in
+   device_tile_error[t] unless that is NULL.  A tile is dropped when
+   b >= max(2, min_batches) and e_t <= threshold.  Flags and a scan, no
+   atomics: the output is reproducible. */
+int rt_adaptive_select_device(const double *device_s1, const double *device_s2,
+                              const int32_t *device_tile_strata, int32_t batch_strata, const rt_frame *frame,
+                              double threshold, double floor, int32_t min_batches,
+                              const int32_t *device_tiles_in, int32_t n_in, int32_t *device_tiles_out,
+                              int32_t *device_count_out, double *device_tile_error, void *hip_stream);
+
+/* rt_to_bytes_device over a frame ([H][W][3]) with the scale
+   1 / max(1, tile_strata[tile of the pixel]) per pixel. */
+int rt_to_bytes_tiles_device(const double *device_rgb, const int32_t *device_tile_strata, const rt_frame *frame,
+                             uint8_t *device_bytes, void *hip_stream);
 
 /* ---- tile exchange (multi-GPU tile sharding) ------------------------------ */
 /* Tile-layout chunk partials [tile][chunk][64][3] (rt_render_device with

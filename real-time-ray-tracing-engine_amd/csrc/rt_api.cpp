@@ -60,6 +60,20 @@ extern "C" hipError_t rtk_launch_shard_finish(const double *parts, int n_local, 
 extern "C" hipError_t rtk_launch_tiles_to_frame(const double *tiles, int n_shards, int64_t shard_stride,
                                                 int W, int row_begin, int row_end, double scale, int scaled,
                                                 int accumulate, double *out, hipStream_t stream);
+// adaptive sampling (rt_adaptive.hip)
+extern "C" hipError_t rtk_launch_tile_list_copy(const int32_t *in, int n, int tiles, int32_t *out,
+                                                hipStream_t stream);
+extern "C" hipError_t rtk_launch_adaptive_update(const double *delta, int batch_strata, const int32_t *list,
+                                                 int n_tiles, int W, int H, double *acc, double *s1,
+                                                 double *s2, int32_t *tile_strata, hipStream_t stream);
+extern "C" hipError_t rtk_launch_adaptive_select(const double *s1, const double *s2,
+                                                 const int32_t *tile_strata, int batch_strata, int W, int H,
+                                                 double threshold, double floor_, int min_batches,
+                                                 const int32_t *list, int n_in, int32_t *out,
+                                                 int32_t *count_out, double *tile_error,
+                                                 hipStream_t stream);
+extern "C" hipError_t rtk_launch_to_bytes_tiles(const double *rgb, const int32_t *tile_strata, int W, int H,
+                                                uint8_t *bytes, hipStream_t stream);
 
 struct rt_scene {
   int device = 0;
@@ -100,6 +114,11 @@ struct rt_scene {
   static constexpr int kOrderSlots = 4;
   OrderSlot order[kOrderSlots];
   uint64_t order_clock = 0;
+  // the caller's tile list of a tile-list launch (rt_render_tiles_device),
+  // copied and clamped on the device: that launch's dispatch order.  Its own
+  // buffer, outside the order slots: a list changes at every reselection
+  int32_t *list_order = nullptr;
+  int list_cap = 0;
   // The scene's launches form one chain across streams: `last` is recorded
   // after each call's last kernel on its stream, and a launch on another
   // stream first waits for it (order_after_last) -- the launches share the
@@ -649,6 +668,7 @@ int rt_scene_destroy(rt_scene *s) {
   bury(s, s->out_buf);
   bury(s, s->scratch);
   bury(s, s->probe_buf);
+  bury(s, s->list_order);
   for (auto &o : s->order) {
     bury(s, o.tile_cost);
     bury(s, o.tile_order[0]);
@@ -910,9 +930,12 @@ static int tile_order_probe(rt_scene *s, const DCamera &C, const DLaunch &L, con
 // (rt_multi_render's shards, reproducing the one-device frame's units).
 // *order_used: the dispatch order the launch used (null: plan order) -- what a
 // finish kernel run after it must map the plan's tiles with.
+// list: a tile-list launch (rt_render_tiles_device) -- the plan's k-th tile is
+// list[k] (the scene's clamped copy of the caller's list), which takes the
+// place of a dispatch order: no probe, no order slot.
 static int launch(rt_scene *s, const DCamera &C, const DLaunch &L, double *dev_out,
                   unsigned long long *stats, hipStream_t st, const SplitPlan *forced = nullptr,
-                  const int32_t **order_used = nullptr) {
+                  const int32_t **order_used = nullptr, const int32_t *list = nullptr) {
   if (order_used) *order_used = nullptr;
   const SplitPlan sp = forced ? *forced : stats ? SplitPlan{L.n_local_tiles, 1, 1} : frame_plan(s, L);
   const size_t n_parts = plan_parts(sp, L.n_local_tiles);
@@ -938,7 +961,7 @@ static int launch(rt_scene *s, const DCamera &C, const DLaunch &L, double *dev_o
   // C4 0.90 -> 0.81 ms per frame, C2 0.222 -> 0.212, r06aa_ab_progressive.log),
   // now that the costs are measured once per shape, not by every launch.
   const bool ordered = !s->tune.no_tile_order && stats == nullptr && (forced || !L.parts_final) &&
-                       L.n_local_tiles > 1;
+                       L.n_local_tiles > 1 && list == nullptr;
   const int32_t sig[10] = {L.n_local_tiles, L.tile_first, L.tile_stride, L.tiles_x, L.row_begin,
                            L.row_end,       L.sample_count, sp.n_head,   sp.head_chunks, sp.chunks};
   // after the scene's previous launch, whichever stream it ran on
@@ -961,7 +984,7 @@ static int launch(rt_scene *s, const DCamera &C, const DLaunch &L, double *dev_o
     if (!kernel_costs && !os->ready && (rc = tile_order_probe(s, C, L, sp, os, st))) return rc;
     Lp.tile_order = os->ready ? os->tile_order[os->cur] : nullptr;
   } else {
-    Lp.tile_order = nullptr;
+    Lp.tile_order = list;
   }
   Lp.tile_cost = nullptr;
   if (kernel_costs) {
@@ -1062,6 +1085,105 @@ int rt_render_device(rt_scene *s, const rt_frame *f, const rt_render_params *p, 
                                          order, dev_rgb, st);
   if (e != hipSuccess) return hip_err(e, "tile chunk sum");
   return mark_last(s, st); // the chunk sum reads the scratch: the chain ends after it
+}
+
+// ---------------------------------------------------------------- adaptive sampling
+// A frame-layout launch over the tiles of a device-resident list: the frame
+// launch over n_tiles tiles whose k-th tile is list[k] -- the render kernel's
+// and split_sum_kernel's own tile indirection (DLaunch.tile_order), fed with
+// the scene's clamped copy of the list instead of a measured dispatch order.
+int rt_render_tiles_device(rt_scene *s, const rt_frame *f, const rt_render_params *p,
+                           const int32_t *device_tiles, int32_t n_tiles, double *dev_rgb,
+                           void *hip_stream) {
+  if (!s || !dev_rgb || !p || !f) return set_err(RT_ERR_INVALID, "null argument");
+  if (p->tile_first != 0 || (p->tile_stride != 0 && p->tile_stride != 1) || p->layout != RT_LAYOUT_FRAME ||
+      p->strata_chunks != 0)
+    return set_err(RT_ERR_INVALID, "a tile-list launch takes tile_first 0, tile_stride 0 or 1, "
+                                   "RT_LAYOUT_FRAME, strata_chunks 0");
+  DCamera C;
+  DLaunch L;
+  int rc = to_device_camera(f, C);
+  if (rc) return rc;
+  if ((rc = to_launch(f, p, L))) return rc;
+  const int64_t tiles = (int64_t)L.tiles_x * L.tiles_y;
+  if (n_tiles < 0 || n_tiles > tiles) return set_err(RT_ERR_INVALID, "n_tiles outside [0, tiles of the row range]");
+  if (n_tiles == 0) return RT_OK; // nothing listed: nothing queued
+  if (!device_tiles) return set_err(RT_ERR_INVALID, "null tile list");
+  DeviceGuard g(s->device);
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (s->list_cap < tiles) { // sized for the whole range: the lists of a frame only shrink
+    if (s->list_order) wait_scene(s); // this scene's launches on any stream may still read it
+    scene_free(s, s->list_order);
+    s->list_cap = 0;
+    hipError_t ae = scene_alloc(s, (void **)&s->list_order, (size_t)tiles * sizeof(int32_t));
+    if (ae != hipSuccess)
+      return set_err(RT_ERR_OOM, std::string("hipMallocFromPoolAsync tile list: ") + hipGetErrorString(ae));
+    s->list_cap = (int)tiles;
+  }
+  // the copy overwrites what the scene's previous tile-list launch may still read
+  if ((rc = order_after_last(s, st))) return rc;
+  hipError_t e = rtk_launch_tile_list_copy(device_tiles, n_tiles, (int)tiles, s->list_order, st);
+  if (e != hipSuccess) return hip_err(e, "tile list copy");
+  L.n_local_tiles = n_tiles; // tile_first 0, tile_stride 1: the mapped tile is the frame's
+  L.n_head = n_tiles;
+  return launch(s, C, L, dev_rgb, nullptr, st, nullptr, nullptr, s->list_order);
+}
+
+static int frame_tiles(const rt_frame *f, int64_t &tiles) {
+  if (!f || f->image_width < 1 || f->image_height < 1) return set_err(RT_ERR_INVALID, "invalid frame");
+  tiles = (int64_t)((f->image_width + 7) / 8) * ((f->image_height + 7) / 8);
+  if (tiles > 0x7FFFFFFF) return set_err(RT_ERR_UNSUPPORTED, "too many tiles");
+  return RT_OK;
+}
+
+int rt_adaptive_update_device(const double *device_delta, int32_t batch_strata, const int32_t *device_tiles,
+                              int32_t n_tiles, const rt_frame *f, double *device_acc, double *device_s1,
+                              double *device_s2, int32_t *device_tile_strata, void *hip_stream) {
+  int64_t tiles = 0;
+  if (int rc = frame_tiles(f, tiles)) return rc;
+  if (!device_delta || !device_acc || !device_s1 || !device_s2 || !device_tile_strata)
+    return set_err(RT_ERR_INVALID, "null argument");
+  if (batch_strata < 1) return set_err(RT_ERR_INVALID, "batch_strata must be >= 1");
+  if (n_tiles < 0 || n_tiles > tiles) return set_err(RT_ERR_INVALID, "n_tiles outside [0, tiles of the frame]");
+  if (n_tiles == 0) return RT_OK;
+  if (!device_tiles) return set_err(RT_ERR_INVALID, "null tile list");
+  hipError_t e = rtk_launch_adaptive_update(device_delta, batch_strata, device_tiles, n_tiles, f->image_width,
+                                            f->image_height, device_acc, device_s1, device_s2,
+                                            device_tile_strata, (hipStream_t)hip_stream);
+  if (e != hipSuccess) return hip_err(e, "adaptive update launch");
+  return RT_OK;
+}
+
+int rt_adaptive_select_device(const double *device_s1, const double *device_s2,
+                              const int32_t *device_tile_strata, int32_t batch_strata, const rt_frame *f,
+                              double threshold, double floor, int32_t min_batches,
+                              const int32_t *device_tiles_in, int32_t n_in, int32_t *device_tiles_out,
+                              int32_t *device_count_out, double *device_tile_error, void *hip_stream) {
+  int64_t tiles = 0;
+  if (int rc = frame_tiles(f, tiles)) return rc;
+  if (!device_s1 || !device_s2 || !device_tile_strata || !device_tiles_out || !device_count_out)
+    return set_err(RT_ERR_INVALID, "null argument");
+  if (batch_strata < 1) return set_err(RT_ERR_INVALID, "batch_strata must be >= 1");
+  if (n_in < 0 || n_in > tiles) return set_err(RT_ERR_INVALID, "n_in outside [0, tiles of the frame]");
+  if (n_in > 0 && !device_tiles_in) return set_err(RT_ERR_INVALID, "null tile list");
+  if (device_tiles_in == device_tiles_out) return set_err(RT_ERR_INVALID, "tiles_out must not alias tiles_in");
+  hipError_t e = rtk_launch_adaptive_select(device_s1, device_s2, device_tile_strata, batch_strata,
+                                            f->image_width, f->image_height, threshold, floor, min_batches,
+                                            device_tiles_in, n_in, device_tiles_out, device_count_out,
+                                            device_tile_error, (hipStream_t)hip_stream);
+  if (e != hipSuccess) return hip_err(e, "adaptive select launch");
+  return RT_OK;
+}
+
+int rt_to_bytes_tiles_device(const double *device_rgb, const int32_t *device_tile_strata, const rt_frame *f,
+                             uint8_t *device_bytes, void *hip_stream) {
+  int64_t tiles = 0;
+  if (int rc = frame_tiles(f, tiles)) return rc;
+  if (!device_rgb || !device_tile_strata || !device_bytes) return set_err(RT_ERR_INVALID, "null argument");
+  hipError_t e = rtk_launch_to_bytes_tiles(device_rgb, device_tile_strata, f->image_width, f->image_height,
+                                           device_bytes, (hipStream_t)hip_stream);
+  if (e != hipSuccess) return hip_err(e, "to_bytes_tiles launch");
+  return RT_OK;
 }
 
 int rt_render_stats(rt_scene *s, const rt_frame *f, const rt_render_params *p,

@@ -164,4 +164,6 @@ EXPORTS = (
     "rt_multi_create", "rt_multi_render", "rt_multi_shard_ms", "rt_multi_destroy",
     "rt_scene_bvh_cost", "rt_tiles_sum_device", "rt_tiles_to_frame_device", "rt_multi_gather_ms",
     "rt_scene_create_tuned", "rt_multi_create_tuned",
+    "rt_render_tiles_device", "rt_adaptive_update_device", "rt_adaptive_select_device",
+    "rt_to_bytes_tiles_device",
 )

@@ -62,6 +62,14 @@ def load():
     L.rt_tiles_to_frame_device.argtypes = [C.c_void_p, C.c_int32, C.c_int64, P(abi.Frame),
                                            P(abi.RenderParams), C.c_void_p, C.c_void_p]
     L.rt_multi_gather_ms.argtypes = [C.c_void_p, P(C.c_double)]
+    L.rt_render_tiles_device.argtypes = [C.c_void_p, P(abi.Frame), P(abi.RenderParams), C.c_void_p,
+                                         C.c_int32, C.c_void_p, C.c_void_p]
+    L.rt_adaptive_update_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, P(abi.Frame),
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rt_adaptive_select_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, P(abi.Frame),
+                                            C.c_double, C.c_double, C.c_int32, C.c_void_p, C.c_int32,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rt_to_bytes_tiles_device.argtypes = [C.c_void_p, C.c_void_p, P(abi.Frame), C.c_void_p, C.c_void_p]
     for name in abi.EXPORTS:
         getattr(L, name).restype = C.c_char_p if name == "rt_last_error" else C.c_int
     if L.rt_abi_version() != abi.RT_ABI_VERSION:

@@ -120,6 +120,16 @@ class Renderer:
         check(self.lib.rt_render_device(self.handle, C.byref(frame), C.byref(p),
                                         C.c_void_p(dev_ptr), C.c_void_p(stream_ptr or 0)))
 
+    def render_tiles_device(self, frame, tiles_ptr, n_tiles, dev_ptr, stream_ptr=None, seed=0,
+                            rows=(0, 0), samples=(0, -1), output=abi.RT_OUT_SUM, accumulate=1):
+        """render_device (frame layout) restricted to the `n_tiles` 8x8 tiles
+        whose row-major indices stand, ascending, in the device int32 array at
+        `tiles_ptr` (rt_render_tiles_device); other pixels stay untouched."""
+        p = self.params(seed, rows, samples, output, accumulate, chunks=0)
+        check(self.lib.rt_render_tiles_device(self.handle, C.byref(frame), C.byref(p),
+                                              C.c_void_p(tiles_ptr), int(n_tiles),
+                                              C.c_void_p(dev_ptr), C.c_void_p(stream_ptr or 0)))
+
     def stats(self, frame, seed=0, rows=(0, 0), samples=(0, -1), tiles=(0, 1),
               layout=abi.RT_LAYOUT_FRAME, chunks=1):
         s = abi.PathStats()
