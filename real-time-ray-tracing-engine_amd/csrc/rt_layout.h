@@ -201,7 +201,7 @@ struct DScene {      // kernel argument (by value)
   int32_t n_mitems;
   int32_t stack_depth;   // per-lane traversal stack entries (BVH depth + 1)
   int32_t n_lds_nodes;   // nodes [0, n_lds_nodes) are staged in LDS (BFS order: top levels)
-  int32_t static_spheres; // 1: every sphere has c1 == c0 (no motion blur): center = c0
+  int32_t static_spheres; // 1: every sphere has c1 == c0 (no motion blur): flat worlds take the center = c0 code
   int32_t n_lds_nodes_pc; // nodes staged by the persistent instance's blocks (-1: none)
   int32_t lds_items_pc;   // world items [0, n) and spheres [0, lds_spheres_pc) the persistent
   int32_t lds_spheres_pc; // instance stages after its nodes (0: primitives stay in HBM)

@@ -455,10 +455,15 @@ RT_HD V3 tex_value(const DScene &S, int t, V3 p) {
 // ------------------------------------------------------------ primitives
 // Sphere::hit root search (Sphere.cpp:101-127).
 // The center at the ray's time, center.at(time) = c0 + tm * (c1 - c0): exactly
-// c0 for a static sphere (dir = 0), so scenes without motion skip the six ops
-// (DScene::static_spheres, wave-uniform).
-RT_HD RT_FI V3 sphere_center(const DSphere &s, double tm, bool moving) {
-  if (!moving) return ld3(s.c0);
+// c0 for a static sphere (dir = 0), so the static form (MOVING = false) has no
+// center arithmetic at all.  MOVING is a compile-time property of the call
+// site (trace's flat walk, trace_tail's record): as a run-time flag the
+// compiler if-converted it and computed c0 + tm * dir for every test before
+// selecting c0 (6 fp64 ops, 6 moves and 6 selects per sphere test;
+// profiles/r07a_static_blocks.md).
+template <bool MOVING = true>
+RT_HD RT_FI V3 sphere_center(const DSphere &s, double tm) {
+  if constexpr (!MOVING) return ld3(s.c0);
   return v3(s.c0[0] + tm * s.dir[0], s.c0[1] + tm * s.dir[1], s.c0[2] + tm * s.dir[2]);
 }
 // x / b from y = RN(1/b): q = x*y is within one ulp of x/b, the remainder
@@ -483,10 +488,11 @@ RT_HD RT_FI double div_mk(double x, double b, double y) {
 }
 constexpr double kInvPi = 1.0 / kPi; // correctly rounded at compile time
 
+template <bool MOVING = true>
 RT_HD RT_FI bool sphere_root(const DSphere &s, const Ray &r, double a, double tmin,
-                                            double tmax, double &root, bool moving = true,
-                                            bool mk = false, double ya = 0.0) {
-  V3 cc = sphere_center(s, r.tm, moving);
+                                            double tmax, double &root, bool mk = false,
+                                            double ya = 0.0) {
+  V3 cc = sphere_center<MOVING>(s, r.tm);
   V3 oc = cc - r.o;
   double h = dot(r.d, oc);
   double c = len2(oc) - s.rr;
@@ -502,9 +508,10 @@ RT_HD RT_FI bool sphere_root(const DSphere &s, const Ray &r, double a, double tm
   root = t;
   return true;
 }
+template <bool MOVING = true>
 RT_HD RT_FI void sphere_record(const DSphere &s, const Ray &r, double t, int mat,
-                                              Hit &h, bool moving = true) {
-  V3 cc = sphere_center(s, r.tm, moving);
+                                              Hit &h) {
+  V3 cc = sphere_center<MOVING>(s, r.tm);
   h.t = t;
   h.p = at(r, t);
   V3 on = s.inv_r * (h.p - cc); // inv_r = 1 / r, the same double the reference forms
@@ -1353,7 +1360,6 @@ RT_HD RT_FI bool trace_tail(const DScene &S, const Ray &r, Hit &h, const Key &ke
                                            Counters &cnt, const LdsPrims &lp = LdsPrims{}) {
   const double tmin = 0.001;
   constexpr bool kFlat = (F & F_FLAT) != 0;
-  const bool moving = kFlat ? !S.static_spheres : true;
   bool best_full = false;
   if constexpr ((F & F_MEDIA) != 0) {
     const uint64_t t0 = STATS ? clk() : 0;
@@ -1387,19 +1393,29 @@ RT_HD RT_FI bool trace_tail(const DScene &S, const Ray &r, Hit &h, const Key &ke
     if (STATS && wave_once()) cnt.cmedia += clk() - t0;
   }
   if (best < 0) return false;
-  if (!best_full) {
+  // the winning item's record; mv: sphere_center's form (see trace's flat walk)
+  auto item_record = [&](auto mv) {
     const DItem it = load_item<LP>(S, lp, best);
     Ray lr = r;
     if constexpr ((F & F_XFORM) != 0) {
       if (it.xf_count) lr = to_local(S, it.xf_first, it.xf_count, r);
     }
     if (it.kind == I_SPHERE)
-      sphere_record(load_sphere<LP>(S, lp, it.idx), lr, closest, it.mat, h, moving);
+      sphere_record<decltype(mv)::value>(load_sphere<LP>(S, lp, it.idx), lr, closest, it.mat, h);
     else
       quad_record(S.quads[it.idx], lr, closest, it.mat, h);
     if constexpr ((F & F_XFORM) != 0) {
       if (it.xf_count) to_world(S, it.xf_first, it.xf_count, h);
     }
+  };
+  if (!best_full) {
+    if constexpr (kFlat) {
+      if (S.static_spheres) { // wave-uniform: a scalar branch, as in the flat walk
+        item_record(UTag<false>{});
+        return true;
+      }
+    }
+    item_record(UTag<true>{});
   }
   return true;
 }
@@ -1422,11 +1438,9 @@ RT_HD RT_FI bool trace(const DScene &S, const Ray &r, Hit &h, const Key &key,
   const double a = len2(r.d);
   const double ya = 1.0 / a; // one reciprocal per ray for every sphere root
   // F_FLAT instances (small worlds, SAH root is one leaf) have no BVH walk; they
-  // need the fp32 slab constants only for the medium box cull, and they skip
-  // the center.at(time) arithmetic when no sphere moves (a wave-uniform flag).
+  // need the fp32 slab constants only for the medium box cull.
   constexpr bool kFlat = (F & F_FLAT) != 0;
   constexpr bool kBoxes = !kFlat || (F & F_MEDIA) != 0;
-  const bool moving = kFlat ? !S.static_spheres : true;
   constexpr bool kFma = !kFlat;
   RayF<kFma> q{};
   float tmin32 = 0.0f;
@@ -1438,10 +1452,13 @@ RT_HD RT_FI bool trace(const DScene &S, const Ray &r, Hit &h, const Key &key,
 
   // hit test of world item ii against ray rr (|d|^2 = ra, its reciprocal ry)
   // in (tmin, tmax): the root in t
-  // (uniform: UTag<true> where ii is the same in every lane -- the flat walk)
-  auto item_root_t = [&](auto uniform, int ii, const Ray &rr, double ra, double ry, double tmax,
-                         double &t) -> bool {
+  // (uniform: UTag<true> where ii is the same in every lane -- the flat walk;
+  // mv: UTag<false> for sphere_center's static form -- the flat walk of a world
+  // without motion)
+  auto item_root_t = [&](auto uniform, auto mv, int ii, const Ray &rr, double ra, double ry,
+                         double tmax, double &t) -> bool {
     constexpr bool U = decltype(uniform)::value && RT_UNIFORM_LOADS_F(F);
+    constexpr bool MV = decltype(mv)::value;
     const DItem it = U ? ldu<U>(S.items, ii) : load_item<LP>(S, lp, ii);
     Ray lr = rr;
     double al = ra;
@@ -1458,8 +1475,8 @@ RT_HD RT_FI bool trace(const DScene &S, const Ray &r, Hit &h, const Key &key,
       // a local ray has its own |d|^2 and so its own reciprocal (a value, not
       // a pointer to one of two locals: that pointer kept ya in scratch memory)
       const double yl = local ? 1.0 / al : ry;
-      return sphere_root(U ? ldu<U>(S.spheres, it.idx) : load_sphere<LP>(S, lp, it.idx), lr, al,
-                         tmin, tmax, t, moving, true, yl);
+      return sphere_root<MV>(U ? ldu<U>(S.spheres, it.idx) : load_sphere<LP>(S, lp, it.idx), lr,
+                             al, tmin, tmax, t, true, yl);
     }
     if (STATS) cnt.quads++;
     constexpr bool UA = decltype(uniform)::value; // the flat walk: the same quad in every lane
@@ -1468,19 +1485,20 @@ RT_HD RT_FI bool trace(const DScene &S, const Ray &r, Hit &h, const Key &key,
   };
   [[maybe_unused]] auto item_root = [&](int ii, const Ray &rr, double ra, double ry, double tmax,
                                         double &t) -> bool {
-    return item_root_t(UTag<false>{}, ii, rr, ra, ry, tmax, t);
+    return item_root_t(UTag<false>{}, UTag<true>{}, ii, rr, ra, ry, tmax, t);
   };
   // closest-hit test of one world item (records only t and the item index)
-  auto test_item = [&](auto uniform, int ii) {
+  auto test_item_m = [&](auto uniform, auto mv, int ii) {
     if (STATS) cnt.wleaf += wave_once();
     double t;
-    const bool hit = item_root_t(uniform, ii, r, a, ya, closest, t);
+    const bool hit = item_root_t(uniform, mv, ii, r, a, ya, closest, t);
     if (hit) {
       closest = t;
       if constexpr (kBoxes) cl32 = f32_up_c(closest);
       best = ii;
     }
   };
+  [[maybe_unused]] auto test_item = [&](auto uniform, int ii) { test_item_m(uniform, UTag<true>{}, ii); };
 
   [[maybe_unused]] constexpr bool kShare = RT_LEAF_SHARE_F(F);
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -1569,8 +1587,15 @@ RT_HD RT_FI bool trace(const DScene &S, const Ray &r, Hit &h, const Key &key,
 #endif
 
   if constexpr (kFlat) {
-    // the reference's HittableList walk (HittableList.cpp), wave-uniform items
-    for (int ii = 0; ii < S.n_root_items; ++ii) test_item(UTag<true>{}, ii);
+    // the reference's HittableList walk (HittableList.cpp), wave-uniform items.
+    // A world without a moving sphere (DScene::static_spheres, wave-uniform)
+    // runs its own instantiation of the loop: one scalar branch per segment,
+    // outside the item loop, between two loops -- it stays a branch.
+    if (S.static_spheres) {
+      for (int ii = 0; ii < S.n_root_items; ++ii) test_item_m(UTag<true>{}, UTag<false>{}, ii);
+    } else {
+      for (int ii = 0; ii < S.n_root_items; ++ii) test_item_m(UTag<true>{}, UTag<true>{}, ii);
+    }
   } else {
     // Speculative while-while traversal (Aila & Laine 2009, "postponed leaves"):
     // a lane that reaches its first leaf parks it in (lf, ln) and keeps walking

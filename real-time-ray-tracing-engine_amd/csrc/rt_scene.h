@@ -41,8 +41,10 @@ struct HostScene {
   double scene_lo[3] = {0, 0, 0}, scene_hi[3] = {0, 0, 0};
 };
 
-// 1 when no sphere moves (DScene::static_spheres): the kernel then skips the
-// center.at(time) arithmetic, whose result is c0 exactly for these spheres.
+// 1 when no sphere moves (DScene::static_spheres): a flat world then runs the
+// static instantiation of its item walk and hit record (rt_path.h trace,
+// trace_tail), without the center.at(time) arithmetic, whose result is c0
+// exactly for these spheres.  BVH worlds ignore the flag.
 inline int32_t all_spheres_static(const HostScene &H) {
   for (const DSphere &s : H.spheres)
     if (s.dir[0] != 0.0 || s.dir[1] != 0.0 || s.dir[2] != 0.0) return 0;
