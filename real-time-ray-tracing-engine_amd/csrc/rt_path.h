@@ -960,6 +960,19 @@ RT_HD RT_FI float rcp32(float x) {
 }
 constexpr float kSlabGrow = 1.0f + 0x1p-19f;
 constexpr float kInvClamp = 1e30f; // finite 1/d: a 0 * inf NaN would drop a box
+// Domain of "never dropped" (stated once in tests/slab_cases.py, checked for
+// every box-test form on the host and on gfx950): o and d finite with
+// max_a |d_a| in [2^-64, 2^64] -- the kernel's directions lie between
+// Lambertian's 1e-8 guard and camera-ray lengths; below about 2^-91 entry
+// distances pass kInvClamp's 1e30 and boxes are dropped -- and a finite fp32
+// box with lo < hi.  A ray lying exactly in a face plane (d_a == +-0 and
+// o_a == lo_a or hi_a) is outside it: the clamp treats +-0 as +-1e-30, so the
+// ray leaves through the face it lies in (far = -0) and the subtract form
+// culls the box.  That loses no hit: every box that reaches the kernel (node
+// boxes from the host, LBVH and device SAH builders, and mbox) is padded
+// outward by 2^-20 relative + 1e-7 (rt_scene.cpp f32_lo / f32_hi and their
+// device copies), so its primitives lie strictly inside the face planes and
+// such a ray cannot touch them.
 
 // Slab form (FMA): t = fma(plane, 1/d, -P) with P = RN32(o/d) per ray
 // and axis — one fp32 FMA per plane instead of a subtract and a multiply.  P's

@@ -9,11 +9,15 @@
 //   box_span            vs boundary_span (a make_box medium's boundary queries,
 //                       tests/test_medium_box.py; the scene compiled on the host
 //                       by csrc/rt_scene.cpp, linked in)
+//   every fp32 box-test form (slab<>, slab_hit, slab_hit2, slab2_planes,
+//                       slab_planes<2>, <4>; slab_forms.h) on the cases of
+//                       tests/slab_cases.py, tests/test_gpu_slab.py
 // Nothing on the product path links this.
 #include <hip/hip_runtime.h>
 
 #include "../../real-time-ray-tracing-engine_amd/csrc/rt_path.h"
 #include "../../real-time-ray-tracing-engine_amd/csrc/rt_scene.h"
+#include "slab_forms.h"
 
 #include <string>
 #include <vector>
@@ -66,6 +70,26 @@ __global__ void medium_kernel(DScene S, int m, const double *rays, int n, double
   o[4] = g ? g1 : 0.0;
   o[5] = g ? g2 : 0.0;
 }
+// one case per thread, 64 threads per block: each thread stages its nodes, one
+// after the other, in its own 128-B slot of the block's LDS array and reads
+// them back through the walk's loads (slab_forms.h)
+__global__ __launch_bounds__(64) void slab_forms_kernel(const double *o, const double *d,
+                                                        const float *lo, const float *hi,
+                                                        const float *tmin, const float *cl,
+                                                        const SlabNodes *nodes, int n,
+                                                        uint32_t *verdict, float *tl) {
+  __shared__ int4 stage[64 * SLAB_SLOT / 16];
+  const int k = blockIdx.x * 64 + threadIdx.x;
+  if (k >= n) return;
+  float t[SLAB_NV];
+  uint32_t v = 0;
+  const float blo[3] = {lo[3 * k], lo[3 * k + 1], lo[3 * k + 2]};
+  const float bhi[3] = {hi[3 * k], hi[3 * k + 1], hi[3 * k + 2]};
+  slab_forms_case(o + 3 * k, d + 3 * k, blo, bhi, tmin[k], cl[k], nodes + k,
+                  (RT_LDS char *)reinterpret_cast<char *>(stage), (int)threadIdx.x * SLAB_SLOT, v, t);
+  verdict[k] = v;
+  for (int i = 0; i < SLAB_NV; ++i) tl[(size_t)SLAB_NV * k + i] = t[i];
+}
 } // namespace
 
 template <class T>
@@ -104,6 +128,40 @@ extern "C" int devcheck_medium_spans(const rt_scene_desc *desc, int m, const dou
     if (hipDeviceSynchronize() != hipSuccess) rc = -4;
   }
   if (!rc && hipMemcpy(out, b[6], 6 * sizeof(double) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess)
+    rc = -5;
+  for (void *p : b)
+    if (p) (void)hipFree(p);
+  return rc;
+}
+
+// emu_slab_forms (tests/native/rt_emulate.cpp) on the device, one launch:
+// host buffers in, host buffers out.  Returns 0, or a negative code.
+extern "C" int devcheck_slab_forms(const double *o, const double *d, const float *lo,
+                                   const float *hi, const float *tmin, const float *cl, int n,
+                                   uint32_t *verdict, float *tl) {
+  if (n <= 0) return 0;
+  const size_t N = (size_t)n;
+  std::vector<SlabNodes> nodes(N);
+  slab_nodes_all(lo, hi, n, nodes.data());
+  void *b[9] = {};
+  int rc = upload(std::vector<double>(o, o + 3 * N), &b[0]);
+  if (!rc) rc = upload(std::vector<double>(d, d + 3 * N), &b[1]);
+  if (!rc) rc = upload(std::vector<float>(lo, lo + 3 * N), &b[2]);
+  if (!rc) rc = upload(std::vector<float>(hi, hi + 3 * N), &b[3]);
+  if (!rc) rc = upload(std::vector<float>(tmin, tmin + N), &b[4]);
+  if (!rc) rc = upload(std::vector<float>(cl, cl + N), &b[5]);
+  if (!rc) rc = upload(nodes, &b[6]);
+  if (!rc && hipMalloc(&b[7], sizeof(uint32_t) * N) != hipSuccess) rc = -3;
+  if (!rc && hipMalloc(&b[8], sizeof(float) * SLAB_NV * N) != hipSuccess) rc = -3;
+  if (!rc) {
+    hipLaunchKernelGGL(slab_forms_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, (const double *)b[0],
+                       (const double *)b[1], (const float *)b[2], (const float *)b[3],
+                       (const float *)b[4], (const float *)b[5], (const SlabNodes *)b[6], n,
+                       (uint32_t *)b[7], (float *)b[8]);
+    if (hipDeviceSynchronize() != hipSuccess) rc = -4;
+  }
+  if (!rc && (hipMemcpy(verdict, b[7], sizeof(uint32_t) * N, hipMemcpyDeviceToHost) != hipSuccess ||
+              hipMemcpy(tl, b[8], sizeof(float) * SLAB_NV * N, hipMemcpyDeviceToHost) != hipSuccess))
     rc = -5;
   for (void *p : b)
     if (p) (void)hipFree(p);
