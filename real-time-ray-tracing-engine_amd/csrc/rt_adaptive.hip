@@ -16,6 +16,8 @@
 
 #include <stdint.h>
 
+#include "rt_kernels.h"
+
 namespace {
 
 constexpr int kWavesPerBlock = 4;

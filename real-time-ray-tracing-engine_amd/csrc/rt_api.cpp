@@ -21,59 +21,10 @@
 #include <vector>
 
 #include "../../include/rt_api.h"
+#include "rt_kernels.h"
 #include "rt_layout.h"
+#include "rt_plan.h"
 #include "rt_scene.h"
-
-extern "C" hipError_t rtk_launch_render(const DScene *S, const DCamera *C, const DLaunch *P,
-                                        double *out, unsigned long long *stats,
-                                        hipStream_t stream);
-extern "C" hipError_t rtk_lds_plan(int features, int stack_depth, int lds_cap, RtkLdsPlan *plan);
-extern "C" hipError_t rtk_lds_plan_pc(int features, int stack_depth, int force_waves, int *pcw,
-                                      int64_t *free_bytes,
-                                      int *blocks_per_cu);
-extern "C" int rtk_lds_prims_enabled(void);
-extern "C" int rtk_lds_perlin_enabled(void);
-extern "C" size_t rtk_lbvh_temp_bytes(int n);
-extern "C" size_t rtk_sah_temp_bytes(int n);
-extern "C" hipError_t rtk_build_sah(const double *boxes, const DItem *items_in, int n,
-                                    DNode *nodes, DItem *items_out, void *temp,
-                                    size_t temp_bytes, int stack_budget, int *n_nodes,
-                                    int *depth, int *root_leaf, hipStream_t st);
-extern "C" hipError_t rtk_build_lbvh(const double *boxes, const DItem *items_in, int n,
-                                     const double *scene_lo, const double *scene_hi,
-                                     DNode *nodes, DItem *items_out, int *depth_dev, void *temp,
-                                     size_t temp_bytes, hipStream_t st);
-extern "C" hipError_t rtk_launch_render_chunked(const DScene *S, const DCamera *C,
-                                                const DLaunch *P, int n_head, int head_chunks,
-                                                int n_chunks, double *out, double *scratch,
-                                                hipStream_t stream);
-extern "C" hipError_t rtk_launch_to_bytes(const double *rgb, int64_t n, double scale,
-                                          uint8_t *bytes, hipStream_t stream);
-extern "C" hipError_t rtk_launch_tiles_sum(const double *parts, int64_t n_tiles, int chunks, double *out,
-                                           hipStream_t stream);
-extern "C" int rtk_cost_f(int features);
-extern "C" hipError_t rtk_launch_tile_order(const uint32_t *cost, int n, int n_head, int32_t *order,
-                                            hipStream_t stream);
-extern "C" hipError_t rtk_launch_shard_finish(const double *parts, int n_local, int n_head, int head_chunks,
-                                              int n_chunks, const int32_t *order, double *out,
-                                              hipStream_t stream);
-extern "C" hipError_t rtk_launch_tiles_to_frame(const double *tiles, int n_shards, int64_t shard_stride,
-                                                int W, int row_begin, int row_end, double scale, int scaled,
-                                                int accumulate, double *out, hipStream_t stream);
-// adaptive sampling (rt_adaptive.hip)
-extern "C" hipError_t rtk_launch_tile_list_copy(const int32_t *in, int n, int tiles, int32_t *out,
-                                                hipStream_t stream);
-extern "C" hipError_t rtk_launch_adaptive_update(const double *delta, int batch_strata, const int32_t *list,
-                                                 int n_tiles, int W, int H, double *acc, double *s1,
-                                                 double *s2, int32_t *tile_strata, hipStream_t stream);
-extern "C" hipError_t rtk_launch_adaptive_select(const double *s1, const double *s2,
-                                                 const int32_t *tile_strata, int batch_strata, int W, int H,
-                                                 double threshold, double floor_, int min_batches,
-                                                 const int32_t *list, int n_in, int32_t *out,
-                                                 int32_t *count_out, double *tile_error,
-                                                 hipStream_t stream);
-extern "C" hipError_t rtk_launch_to_bytes_tiles(const double *rgb, const int32_t *tile_strata, int W, int H,
-                                                uint8_t *bytes, hipStream_t stream);
 
 struct rt_scene {
   int device = 0;
@@ -104,9 +55,10 @@ struct rt_scene {
   // a scene that alternates tile subsets (several ranks' shares on one
   // device) keeps an order for each instead of probing one slot again
   struct OrderSlot {
-    uint32_t *tile_cost = nullptr;
+    uint32_t *tile_cost = nullptr; // one allocation: the costs, then the two orders
     int32_t *tile_order[2] = {nullptr, nullptr};
-    int cap = 0, cur = 0;
+    size_t bytes = 0;
+    int cur = 0;
     bool ready = false;
     int32_t sig[10] = {};
     uint64_t used = 0; // launch counter at the slot's last use
@@ -118,7 +70,7 @@ struct rt_scene {
   // copied and clamped on the device: that launch's dispatch order.  Its own
   // buffer, outside the order slots: a list changes at every reselection
   int32_t *list_order = nullptr;
-  int list_cap = 0;
+  size_t list_bytes = 0;
   // The scene's launches form one chain across streams: `last` is recorded
   // after each call's last kernel on its stream, and a launch on another
   // stream first waits for it (order_after_last) -- the launches share the
@@ -247,6 +199,25 @@ hipError_t upload(rt_scene *s, void *dst, const void *src, size_t bytes, hipMemc
 void wait_scene(rt_scene *s) {
   if (s->stream) (void)hipStreamSynchronize(s->stream);
   if (s->has_last) (void)hipEventSynchronize(s->last);
+}
+// Grows one of the scene's buffers to `bytes` (its contents are not kept).
+// `idle` says what to wait for before the old buffer is freed -- where the
+// buffers differ: the scene's launches on any stream (what every launch reads:
+// scratch, probe output, tile list, order slots), the scene's own stream only
+// (out_buf, which no other stream writes), or nothing (rt_multi's staging:
+// the last rt_multi_render synchronised every stream that used it).
+enum class Idle { AfterScene, AfterStream, Already };
+template <class T>
+int grow(rt_scene *s, T *&buf, size_t &have, size_t bytes, Idle idle, const char *what) {
+  if (have >= bytes) return RT_OK;
+  if (buf && idle == Idle::AfterScene) wait_scene(s);
+  if (buf && idle == Idle::AfterStream) (void)hipStreamSynchronize(s->stream);
+  scene_free(s, buf);
+  have = 0;
+  hipError_t e = scene_alloc(s, (void **)&buf, bytes);
+  if (e != hipSuccess) return set_err(RT_ERR_OOM, std::string(what) + ": " + hipGetErrorString(e));
+  have = bytes;
+  return RT_OK;
 }
 // before a call's first kernel on st: after the scene's previous launch
 int order_after_last(rt_scene *s, hipStream_t st) {
@@ -669,11 +640,7 @@ int rt_scene_destroy(rt_scene *s) {
   bury(s, s->scratch);
   bury(s, s->probe_buf);
   bury(s, s->list_order);
-  for (auto &o : s->order) {
-    bury(s, o.tile_cost);
-    bury(s, o.tile_order[0]);
-    bury(s, o.tile_order[1]);
-  }
+  for (auto &o : s->order) bury(s, o.tile_cost); // the slot's one allocation
   bury(s, s->block);
   if (s->last) (void)hipEventDestroy(s->last);
   if (s->ev0) (void)hipEventDestroy(s->ev0);
@@ -683,153 +650,8 @@ int rt_scene_destroy(rt_scene *s) {
   return RT_OK;
 }
 
-// Work units of a frame-layout launch over every tile (SplitPlan): the waves
-// should end together, so the launch must end on short units, while every
-// unit pays a refill drain at its end (its last paths finish while lanes
-// idle) and long units pay it less often.
-//  * Frames of more than 4 tiles per resident wave (1080p: 7.9 on 4,096 wave
-//    slots) whose head plan keeps the partials within 4 frames: head tiles
-//    whole (up to 64 strata: written straight into the frame, C2) or in
-//    chunks of 128 strata (C3: 2 per tile), and the last `slots` x
-//    rt_tuning.tail_tiles (default 0.25) tiles in 8x finer chunks, the units the
-//    waves take last (dispatch / counter order), so the launch ends on a
-//    short unit (C2 +3.9 %, C3 +1.2 % over the uniform split;
-//    profiles/r03f_ab.log).  Whole 256-strata tiles as C3's head: -9 %
-//    (r03e_ab.log, r04b_head_strata_ab.log); chunks of 128 strata measure the
-//    same as 64 with half the partial writes (r04b).
-//  * Otherwise every tile split, ~RTX_CHUNK_TARGET (default 32) units per
-//    wave slot (the round-1 rule), the last tiles again in finer chunks.
-// rt_tuning.chunk_target < 0: whole tiles only (tests).
-struct SplitPlan {
-  int n_head, head_chunks, chunks; // head tiles, their chunks; the tail tiles' chunks
-};
-static size_t plan_parts(const SplitPlan &sp, int n_local) { // chunk partial records
-  return (size_t)(sp.head_chunks > 1 ? (int64_t)sp.n_head * sp.head_chunks : 0) +
-         (size_t)(n_local - sp.n_head) * (sp.n_head < n_local ? sp.chunks : 0);
-}
-static SplitPlan frame_plan(const rt_scene *s, const DLaunch &L) {
-  SplitPlan sp{L.n_local_tiles, 1, 1};
-  if (L.compact || L.tile_stride != 1 || L.tile_first != 0 || L.sample_count < 2) return sp;
-  const rt_tuning &tu = s->tune;
-  const int target = tu.chunk_target == 0 ? 32 : tu.chunk_target;
-  if (target <= 0 || s->wave_slots <= 0) return sp;
-  // wave slots of the instance that runs the launch (the persistent one's own
-  // residency for the feature sets that have one)
-  const int64_t tiles = (int64_t)L.n_local_tiles,
-                slots = s->pc_grid > 0 && s->ds.pc_waves > 0 ? (int64_t)s->pc_grid * s->ds.pc_waves : s->wave_slots;
-  auto no_empty = [&](int64_t c) { // chunk count with no empty chunks
-    c = std::max<int64_t>(1, std::min<int64_t>(c, L.sample_count));
-    const int64_t cs = (L.sample_count + c - 1) / c;
-    return (int)((L.sample_count + cs - 1) / cs);
-  };
-  // tail tiles per wave slot: a quarter for the head/tail plan since the head
-  // tiles are taken most expensive first (tile order; C2 +0.9 %, C3 +0.2 %,
-  // profiles/r05x_ab.log), a half after the uniform split (C4 -1.6 % at a
-  // quarter)
-  const double tail_ht = tu.tail_tiles == 0.0 ? 0.25 : std::max(0.0, tu.tail_tiles);
-  const double tail = tu.tail_tiles == 0.0 ? 0.5 : std::max(0.0, tu.tail_tiles);
-  // head units: whole tiles up to 64 strata (C2); beyond, chunks of 128
-  // strata (C3: 2 per tile -- as fast as 4 chunks of 64, half the partial
-  // writes; whole 256-strata tiles -9 %, profiles/r04b_head_strata_ab.log)
-  const int head_max = tu.head_strata > 0 ? (int)tu.head_strata : L.sample_count <= 64 ? 64 : 128;
-  const int64_t head_chunks = (L.sample_count + head_max - 1) / head_max;
-  const int split = tu.tail_split > 0 ? (int)tu.tail_split : 8; // tail chunks per head chunk
-  // partial records of a head/tail plan: bounded by 4 frames (a tail of
-  // chunked tiles + head chunks); otherwise the uniform split
-  const bool bounded = head_chunks == 1 || head_chunks * tiles <= 4 * tiles;
-  if (tiles > 4 * slots && tail > 0 && bounded) {
-    const int64_t n_tail = std::min<int64_t>(tiles, std::max<int64_t>(1, (int64_t)(tail_ht * slots)));
-    sp.head_chunks = no_empty((L.sample_count + head_max - 1) / head_max);
-    sp.chunks = no_empty(split * (int64_t)sp.head_chunks);
-    sp.n_head = (int)(tiles - n_tail);
-    if (sp.chunks <= 1) sp = SplitPlan{L.n_local_tiles, 1, 1};
-    return sp;
-  }
-  const int64_t c = ((int64_t)target * slots + tiles - 1) / std::max<int64_t>(1, tiles);
-  sp.chunks = no_empty(c);
-  if (sp.chunks > 1) sp.n_head = 0;
-  // ... with the last `slots` x rt_tuning.tail_tiles (default 0.5 here) tiles in `split` times finer
-  // chunks when the frame has a tile per wave slot (C4, C5: the uniform
-  // units last 15 / 84 ms: C4 +1.7 %, C5 +0.9 %, profiles/r03ae_ab.log;
-  // rt_tuning.no_uniform_tail: off, A/B runs)
-  if (!tu.no_uniform_tail && sp.chunks > 1 && tiles > slots && tail > 0) {
-    const int64_t n_tail = std::min<int64_t>(tiles, std::max<int64_t>(1, (int64_t)(tail * slots)));
-    const int tc = no_empty(split * (int64_t)sp.chunks);
-    if (tc > sp.chunks && n_tail < tiles) {
-      sp.head_chunks = sp.chunks;
-      sp.chunks = tc;
-      sp.n_head = (int)(tiles - n_tail);
-    }
-  }
-  return sp;
-}
-
-// Work units of a tile-subset launch that returns its tiles' sums
-// (strata_chunks = RT_CHUNKS_AUTO: one rank's share of a tile-sharded frame).
-// A share of more than 4 tiles per wave slot takes the frame plan.  A smaller
-// one (an 8-way rank of a 1080p frame: 4,050 tiles on 4,096 slots) cannot
-// hand whole tiles to the waves -- the slowest tile would be the launch -- so
-// every tile is split into head units of `sub_head_strata` strata, and the
-// last sub_tail_permille / 1000 x slots tiles into `sub_tail_split` times
-// finer chunks, which the waves take last (dispatch / counter order) so the
-// launch ends on short units.  Long units drain less often (a unit ends with
-// its last paths finishing while lanes idle), short ones balance the end.
-// Defaults from 8-way sweeps on one GPU (profiles/r05n_*, r05o_*): head units
-// of 16 x sqrt(strata / 64) strata (C2 16, C3 32, C4 64), a tail of an eighth
-// of the slots' tiles in halves of those: against every tile in the rank's
-// uniform chunks, C2's share -3 to -8 %, C3's -1.5 %, C4's -0.8 % (a quarter
-// then; an eighth since tile order, C2 -3.4 %: profiles/r05x_sim_C2.log).
-constexpr int kSubTailSplit = 2, kSubTailPermille = 125;
-static SplitPlan subset_plan(const rt_scene *s, const DLaunch &L) {
-  SplitPlan sp{L.n_local_tiles, 1, 1};
-  if (L.sample_count < 2 || L.n_local_tiles < 1 || s->wave_slots <= 0) return sp;
-  const rt_tuning &tu = s->tune;
-  const int64_t tiles = (int64_t)L.n_local_tiles,
-                slots = s->pc_grid > 0 && s->ds.pc_waves > 0 ? (int64_t)s->pc_grid * s->ds.pc_waves : s->wave_slots;
-  if (tiles > 4 * slots) {
-    DLaunch F = L;
-    F.compact = 0;
-    F.tile_first = 0;
-    F.tile_stride = 1;
-    return frame_plan(s, F);
-  }
-  auto no_empty = [&](int64_t c) { // chunk count with no empty chunks
-    c = std::max<int64_t>(1, std::min<int64_t>(c, L.sample_count));
-    const int64_t cs = (L.sample_count + c - 1) / c;
-    return (int)((L.sample_count + cs - 1) / cs);
-  };
-  const int head = tu.sub_head_strata > 0
-                       ? tu.sub_head_strata
-                       : std::max(1, (int)std::lround(16.0 * std::sqrt(L.sample_count / 64.0)));
-  const int split = tu.sub_tail_split > 0 ? tu.sub_tail_split : kSubTailSplit;
-  const int permille = tu.sub_tail_permille != 0 ? tu.sub_tail_permille : kSubTailPermille;
-  sp.head_chunks = no_empty((L.sample_count + head - 1) / head);
-  sp.chunks = sp.head_chunks;
-  sp.n_head = (int)tiles;
-  if (permille > 0) {
-    const int64_t n_tail = std::min<int64_t>(tiles, std::max<int64_t>(1, slots * permille / 1000));
-    const int tc = no_empty((int64_t)split * sp.head_chunks);
-    if (tc > sp.head_chunks) {
-      sp.chunks = tc;
-      sp.n_head = (int)(tiles - n_tail);
-    }
-  }
-  if (sp.n_head == 0) sp.head_chunks = 1; // every tile a tail tile
-  return sp;
-}
-
-static int ensure_scratch(rt_scene *s, size_t bytes) {
-  if (s->scratch_bytes >= bytes) return RT_OK;
-  if (s->scratch) {
-    wait_scene(s); // this scene's launches on any stream may still read it
-    scene_free(s, s->scratch);
-    s->scratch_bytes = 0;
-  }
-  hipError_t e = scene_alloc(s, (void **)&s->scratch, bytes);
-  if (e != hipSuccess) return set_err(RT_ERR_OOM, std::string("hipMallocFromPoolAsync scratch: ") + hipGetErrorString(e));
-  s->scratch_bytes = bytes;
-  return RT_OK;
-}
+// what the planners (rt_plan.cpp) read of the scene's device
+static PlanDevice plan_device(const rt_scene *s) { return PlanDevice{s->wave_slots, s->pc_grid, s->ds.pc_waves}; }
 
 // Cost-ordered dispatch ("tile order"): a launch's work units are taken in
 // plan order (head units, then the finer tail chunks -- unit index order is
@@ -862,18 +684,13 @@ static int order_slot(rt_scene *s, const int32_t sig[10], int n, rt_scene::Order
     std::copy(sig, sig + 10, slot->sig);
   }
   slot->used = ++s->order_clock;
-  if (slot->cap >= n) return RT_OK;
-  if (slot->tile_cost) wait_scene(s); // this scene's launches on any stream may still use them
-  scene_free(s, slot->tile_cost);
-  scene_free(s, slot->tile_order[0]);
-  scene_free(s, slot->tile_order[1]);
-  slot->cap = 0;
+  const size_t each = align256((size_t)n * sizeof(int32_t)); // costs, order 0, order 1
+  if (slot->bytes >= 3 * each) return RT_OK;
   slot->ready = false;
-  hipError_t e = scene_alloc(s, (void **)&slot->tile_cost, (size_t)n * sizeof(uint32_t));
-  if (e == hipSuccess) e = scene_alloc(s, (void **)&slot->tile_order[0], (size_t)n * sizeof(int32_t));
-  if (e == hipSuccess) e = scene_alloc(s, (void **)&slot->tile_order[1], (size_t)n * sizeof(int32_t));
-  if (e != hipSuccess) return set_err(RT_ERR_OOM, std::string("hipMallocFromPoolAsync tile order: ") + hipGetErrorString(e));
-  slot->cap = n;
+  if (int rc = grow(s, slot->tile_cost, slot->bytes, 3 * each, Idle::AfterScene, "hipMallocFromPoolAsync tile order"))
+    return rc;
+  slot->tile_order[0] = (int32_t *)((char *)slot->tile_cost + each);
+  slot->tile_order[1] = (int32_t *)((char *)slot->tile_cost + 2 * each);
   return RT_OK;
 }
 
@@ -886,30 +703,20 @@ static int order_slot(rt_scene *s, const int32_t sig[10], int n, rt_scene::Order
 // bookkeeping compiled into them cost C4 12.5 % (r05u_ab.log) and C2 / C3 / C5
 // 0.9 % (r06y_ab_C*.log), while a once-per-shape order ranks the tiles as well
 // as one re-measured after every launch (r06x / r06y).
-static int tile_order_probe(rt_scene *s, const DCamera &C, const DLaunch &L, const SplitPlan &sp,
-                            rt_scene::OrderSlot *os, hipStream_t st) {
+// L: the launch with its plan applied (the sort keeps its head and tail apart).
+static int tile_order_probe(rt_scene *s, const DCamera &C, const DLaunch &L, rt_scene::OrderSlot *os,
+                            hipStream_t st) {
   // 16 strata: C4 +0.2 % over 4 (r06u), C2 +0.6 % / C3 +0.9 % over 4 and 1 (r06aa)
   constexpr int kProbeStrata = 16;
   const size_t bytes = std::max<size_t>(1, (size_t)L.n_local_tiles * 64 * 3) * sizeof(double);
-  if (s->probe_bytes < bytes) {
-    if (s->probe_buf) wait_scene(s);
-    scene_free(s, s->probe_buf);
-    s->probe_bytes = 0;
-    hipError_t ae = scene_alloc(s, (void **)&s->probe_buf, bytes);
-    if (ae != hipSuccess) return set_err(RT_ERR_OOM, std::string("hipMallocFromPoolAsync probe: ") + hipGetErrorString(ae));
-    s->probe_bytes = bytes;
-  }
+  if (int rc = grow(s, s->probe_buf, s->probe_bytes, bytes, Idle::AfterScene, "hipMallocFromPoolAsync probe"))
+    return rc;
   DLaunch Q = L;
   Q.sample_count = std::min(L.sample_count, s->tune.probe_strata > 0 ? s->tune.probe_strata : kProbeStrata);
   Q.output = RT_OUT_SUM;
   Q.accumulate = 0;
   Q.compact = 1;
-  Q.n_head = L.n_local_tiles;
-  Q.head_chunks = 1;
-  Q.n_chunks = 1;
-  Q.chunk_strata = Q.sample_count;
-  Q.parts = nullptr;
-  Q.parts_final = 0;
+  apply_plan(Q, whole_plan(L.n_local_tiles), nullptr, 0);
   Q.unit_ctr = nullptr;
   Q.grid_cap = 0;
   Q.tile_order = nullptr;
@@ -918,7 +725,7 @@ static int tile_order_probe(rt_scene *s, const DCamera &C, const DLaunch &L, con
   if (e == hipSuccess) e = hipMemsetAsync(s->stats, 0, RT_N_STATS * sizeof(unsigned long long), st);
   if (e == hipSuccess) e = rtk_launch_render(&s->ds, &C, &Q, s->probe_buf, s->stats, st);
   if (e == hipSuccess)
-    e = rtk_launch_tile_order(os->tile_cost, L.n_local_tiles, std::min(sp.n_head, L.n_local_tiles),
+    e = rtk_launch_tile_order(os->tile_cost, L.n_local_tiles, std::min(L.n_head, L.n_local_tiles),
                               os->tile_order[os->cur], st);
   if (e != hipSuccess) return hip_err(e, "tile order probe");
   os->ready = true;
@@ -928,26 +735,35 @@ static int tile_order_probe(rt_scene *s, const DCamera &C, const DLaunch &L, con
 // forced: the split plan of a tile-layout launch whose whole tiles go to
 // dev_out (compact) and split tiles' raw partials to the scene's scratch
 // (rt_multi_render's shards, reproducing the one-device frame's units).
-// *order_used: the dispatch order the launch used (null: plan order) -- what a
-// finish kernel run after it must map the plan's tiles with.
+// *launched: the launch as the render kernel got it -- its plan, its partials
+// and the dispatch order it used (null: plan order), what a finish kernel run
+// after it must read.
 // list: a tile-list launch (rt_render_tiles_device) -- the plan's k-th tile is
 // list[k] (the scene's clamped copy of the caller's list), which takes the
 // place of a dispatch order: no probe, no order slot.
 static int launch(rt_scene *s, const DCamera &C, const DLaunch &L, double *dev_out,
-                  unsigned long long *stats, hipStream_t st, const SplitPlan *forced = nullptr,
-                  const int32_t **order_used = nullptr, const int32_t *list = nullptr) {
-  if (order_used) *order_used = nullptr;
-  const SplitPlan sp = forced ? *forced : stats ? SplitPlan{L.n_local_tiles, 1, 1} : frame_plan(s, L);
-  const size_t n_parts = plan_parts(sp, L.n_local_tiles);
-  const bool split = !L.compact && n_parts > 0;
+                  unsigned long long *stats, hipStream_t st, const UnitPlan *forced = nullptr,
+                  DLaunch *launched = nullptr, const int32_t *list = nullptr) {
+  const UnitPlan sp = forced ? *forced
+                      : stats ? whole_plan(L.n_local_tiles)
+                              : frame_plan(plan_device(s), s->tune, L);
+  // forced plans and frame launches take sp (a frame launch's chunk partials
+  // go through the scratch: split); any other tile-layout launch keeps
+  // launch_geometry's plan, its chunk partials being the caller's output
+  DLaunch Lp = L;
+  if (forced || !L.compact) apply_plan(Lp, sp, nullptr, 0);
+  const bool split = !L.compact && plan_parts(Lp) > 0;
   if (split || forced) {
-    int rc = ensure_scratch(s, std::max<size_t>(1, n_parts * 64 * 3) * sizeof(double));
-    if (rc) return rc;
+    const size_t bytes = std::max<size_t>(1, (size_t)plan_parts(Lp) * 64 * 3) * sizeof(double);
+    if (int rc = grow(s, s->scratch, s->scratch_bytes, bytes, Idle::AfterScene, "hipMallocFromPoolAsync scratch"))
+      return rc;
+    apply_plan(Lp, sp, s->scratch, 0);
+  } else if (L.parts_final) {
+    apply_plan(Lp, plan_of(L), dev_out, 1); // tile layout, strata_chunks > 1
   }
   // persistent waves pulling work units (rt_tuning.no_persistent: one unit
   // per wave, for A/B runs)
   const bool persistent = !s->tune.no_persistent;
-  DLaunch Lp = L;
   if (persistent && s->wave_slots > 0) {
     Lp.unit_ctr = s->unit_ctr;
     Lp.grid_cap = s->pc_grid > 0 ? s->pc_grid // resident persistent blocks
@@ -963,7 +779,7 @@ static int launch(rt_scene *s, const DCamera &C, const DLaunch &L, double *dev_o
   const bool ordered = !s->tune.no_tile_order && stats == nullptr && (forced || !L.parts_final) &&
                        L.n_local_tiles > 1 && list == nullptr;
   const int32_t sig[10] = {L.n_local_tiles, L.tile_first, L.tile_stride, L.tiles_x, L.row_begin,
-                           L.row_end,       L.sample_count, sp.n_head,   sp.head_chunks, sp.chunks};
+                           L.row_end,       L.sample_count, sp.n_head,   sp.head_chunks, sp.n_chunks};
   // after the scene's previous launch, whichever stream it ran on
   if (int rc = order_after_last(s, st)) return rc;
   rt_scene::OrderSlot *os = nullptr;
@@ -981,7 +797,7 @@ static int launch(rt_scene *s, const DCamera &C, const DLaunch &L, double *dev_o
     int rc = order_slot(s, sig, L.n_local_tiles, os);
     if (rc) return rc;
     if (os->ready) kernel_costs = false;
-    if (!kernel_costs && !os->ready && (rc = tile_order_probe(s, C, L, sp, os, st))) return rc;
+    if (!kernel_costs && !os->ready && (rc = tile_order_probe(s, C, Lp, os, st))) return rc;
     Lp.tile_order = os->ready ? os->tile_order[os->cur] : nullptr;
   } else {
     Lp.tile_order = list;
@@ -994,24 +810,13 @@ static int launch(rt_scene *s, const DCamera &C, const DLaunch &L, double *dev_o
   }
   hipError_t e = hipEventRecord(s->ev0, st);
   if (e != hipSuccess) return hip_err(e, "hipEventRecord");
-  if (forced) {
-    Lp.n_head = sp.n_head;
-    Lp.head_chunks = sp.head_chunks;
-    Lp.n_chunks = sp.chunks;
-    Lp.chunk_strata = (L.sample_count + sp.chunks - 1) / sp.chunks;
-    Lp.parts = s->scratch;
-    Lp.parts_final = 0;
-  } else if (L.parts_final) {
-    Lp.parts = dev_out; // tile layout, strata_chunks > 1: the chunk partials are the output
-  }
-  e = split ? rtk_launch_render_chunked(&s->ds, &C, &Lp, sp.n_head, sp.head_chunks, sp.chunks, dev_out,
-                                        s->scratch, st)
-            : rtk_launch_render(&s->ds, &C, &Lp, dev_out, stats, st);
+  e = rtk_launch_render(&s->ds, &C, &Lp, dev_out, stats, st);
+  if (e == hipSuccess && split) e = rtk_launch_split_sum(&C, &Lp, dev_out, st); // chunk partials into the frame
   if (e != hipSuccess) return hip_err(e, "render kernel launch");
   e = hipEventRecord(s->ev1, st);
   if (e != hipSuccess) return hip_err(e, "hipEventRecord");
   s->timed = true;
-  if (order_used) *order_used = Lp.tile_order;
+  if (launched) *launched = Lp;
   if (kernel_costs) { // the next launch's order, into the buffer this one did not read
     const int next = os->cur ^ 1;
     e = rtk_launch_tile_order(os->tile_cost, L.n_local_tiles, std::min(sp.n_head, L.n_local_tiles),
@@ -1023,17 +828,8 @@ static int launch(rt_scene *s, const DCamera &C, const DLaunch &L, double *dev_o
   return mark_last(s, st);
 }
 
-static int ensure_out(rt_scene *s, size_t bytes) {
-  if (s->out_bytes >= bytes) return RT_OK;
-  if (s->out_buf) {
-    (void)hipStreamSynchronize(s->stream); // only the scene's own stream writes it
-    scene_free(s, s->out_buf);
-    s->out_bytes = 0;
-  }
-  hipError_t e = scene_alloc(s, (void **)&s->out_buf, bytes);
-  if (e != hipSuccess) return set_err(RT_ERR_OOM, std::string("hipMallocFromPoolAsync output: ") + hipGetErrorString(e));
-  s->out_bytes = bytes;
-  return RT_OK;
+static int ensure_out(rt_scene *s, size_t bytes) { // only the scene's own stream writes out_buf
+  return grow(s, s->out_buf, s->out_bytes, bytes, Idle::AfterStream, "hipMallocFromPoolAsync output");
 }
 
 int rt_render(rt_scene *s, const rt_frame *f, const rt_render_params *p, double *host_rgb) {
@@ -1078,11 +874,10 @@ int rt_render_device(rt_scene *s, const rt_frame *f, const rt_render_params *p, 
   // the subset's own units: whole head tiles straight into dev_rgb, chunk
   // partials into the scratch, added in chunk order into dev_rgb (the
   // rt_multi shards' finish), all on `st`
-  const SplitPlan sp = subset_plan(s, L);
-  const int32_t *order = nullptr;
-  if ((rc = launch(s, C, L, dev_rgb, nullptr, st, &sp, &order))) return rc;
-  hipError_t e = rtk_launch_shard_finish(s->scratch, L.n_local_tiles, sp.n_head, sp.head_chunks, sp.chunks,
-                                         order, dev_rgb, st);
+  const UnitPlan sp = subset_plan(plan_device(s), s->tune, L);
+  DLaunch done;
+  if ((rc = launch(s, C, L, dev_rgb, nullptr, st, &sp, &done))) return rc;
+  hipError_t e = rtk_launch_shard_finish(&done, dev_rgb, st);
   if (e != hipSuccess) return hip_err(e, "tile chunk sum");
   return mark_last(s, st); // the chunk sum reads the scratch: the chain ends after it
 }
@@ -1111,21 +906,16 @@ int rt_render_tiles_device(rt_scene *s, const rt_frame *f, const rt_render_param
   if (!device_tiles) return set_err(RT_ERR_INVALID, "null tile list");
   DeviceGuard g(s->device);
   hipStream_t st = (hipStream_t)hip_stream;
-  if (s->list_cap < tiles) { // sized for the whole range: the lists of a frame only shrink
-    if (s->list_order) wait_scene(s); // this scene's launches on any stream may still read it
-    scene_free(s, s->list_order);
-    s->list_cap = 0;
-    hipError_t ae = scene_alloc(s, (void **)&s->list_order, (size_t)tiles * sizeof(int32_t));
-    if (ae != hipSuccess)
-      return set_err(RT_ERR_OOM, std::string("hipMallocFromPoolAsync tile list: ") + hipGetErrorString(ae));
-    s->list_cap = (int)tiles;
-  }
+  // sized for the whole range: the lists of a frame only shrink
+  if ((rc = grow(s, s->list_order, s->list_bytes, (size_t)tiles * sizeof(int32_t), Idle::AfterScene,
+                 "hipMallocFromPoolAsync tile list")))
+    return rc;
   // the copy overwrites what the scene's previous tile-list launch may still read
   if ((rc = order_after_last(s, st))) return rc;
   hipError_t e = rtk_launch_tile_list_copy(device_tiles, n_tiles, (int)tiles, s->list_order, st);
   if (e != hipSuccess) return hip_err(e, "tile list copy");
   L.n_local_tiles = n_tiles; // tile_first 0, tile_stride 1: the mapped tile is the frame's
-  L.n_head = n_tiles;
+  apply_plan(L, whole_plan(n_tiles), nullptr, 0);
   return launch(s, C, L, dev_rgb, nullptr, st, nullptr, nullptr, s->list_order);
 }
 
@@ -1204,8 +994,8 @@ int rt_render_stats(rt_scene *s, const rt_frame *f, const rt_render_params *p,
   if ((rc = ensure_out(s, n * sizeof(double)))) return rc;
   hipError_t e = hipMemsetAsync(s->stats, 0, RT_N_STATS * sizeof(unsigned long long), s->stream);
   if (e != hipSuccess) return hip_err(e, "hipMemsetAsync stats");
-  SplitPlan sp{};
-  if (auto_units) sp = subset_plan(s, L);
+  UnitPlan sp{};
+  if (auto_units) sp = subset_plan(plan_device(s), s->tune, L);
   if ((rc = launch(s, C, L, s->out_buf, s->stats, s->stream, auto_units ? &sp : nullptr))) return rc;
   unsigned long long h[RT_N_STATS];
   e = hipMemcpyAsync(h, s->stats, sizeof h, hipMemcpyDeviceToHost, s->stream);
@@ -1420,7 +1210,7 @@ int rt_multi_create_tuned(const rt_scene_desc *desc, const int32_t *devices, int
 // the root's staging slot `dst`.  *t_done: host clock (ms) when the render and
 // finish kernels had completed.
 static int render_shard(rt_scene *s, const rt_frame *f, const rt_render_params *p, int first, int stride,
-                        const SplitPlan &plan, double *dst, int root_dev, double *t_done) {
+                        const UnitPlan &plan, double *dst, int root_dev, double *t_done) {
   DCamera C;
   DLaunch L;
   rt_render_params q = *p;
@@ -1433,15 +1223,13 @@ static int render_shard(rt_scene *s, const rt_frame *f, const rt_render_params *
   int rc = to_device_camera(f, C);
   if (rc) return rc;
   if ((rc = to_launch(f, &q, L))) return rc;
-  SplitPlan sp = plan;
-  sp.n_head = plan.n_head > first ? std::min(L.n_local_tiles, (plan.n_head - first + stride - 1) / stride) : 0;
+  const UnitPlan sp = shard_plan(plan, first, stride, L.n_local_tiles);
   DeviceGuard g(s->device);
   const size_t nt = (size_t)L.n_local_tiles * 64 * 3;
   if ((rc = ensure_out(s, std::max<size_t>(nt, 1) * sizeof(double)))) return rc;
-  const int32_t *order = nullptr;
-  if ((rc = launch(s, C, L, s->out_buf, nullptr, s->stream, &sp, &order))) return rc;
-  hipError_t e = rtk_launch_shard_finish(s->scratch, L.n_local_tiles, sp.n_head, sp.head_chunks, sp.chunks,
-                                         order, s->out_buf, s->stream);
+  DLaunch done;
+  if ((rc = launch(s, C, L, s->out_buf, nullptr, s->stream, &sp, &done))) return rc;
+  hipError_t e = rtk_launch_shard_finish(&done, s->out_buf, s->stream);
   if (e == hipSuccess && (rc = mark_last(s, s->stream))) return rc;
   if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
   if (e != hipSuccess) return hip_err(e, "shard render");
@@ -1471,29 +1259,20 @@ int rt_multi_render(rt_multi *m, const rt_frame *f, const rt_render_params *p, d
   rt_scene *root = m->scenes[0];
   // the one-device frame launch's units (so the frame is bit-identical to
   // rt_render on one device), or every tile in strata_chunks chunks if asked
-  SplitPlan plan = frame_plan(root, L);
-  if (p->strata_chunks > 0)
-    plan = SplitPlan{0, 1, std::max(1, std::min(p->strata_chunks, std::max(1, L.sample_count)))};
+  const UnitPlan plan = p->strata_chunks > 0 ? chunks_plan(p->strata_chunks, L.sample_count)
+                                             : frame_plan(plan_device(root), root->tune, L);
   const int64_t n_tiles = (int64_t)L.tiles_x * L.tiles_y;
   const int64_t stride = (n_tiles + n - 1) / n; // staging slot per shard, in tiles
   const size_t frame_d = (size_t)(L.row_end - L.row_begin) * f->image_width * 3;
   {
     DeviceGuard g(root->device);
-    auto grow = [&](double *&buf, size_t &have, size_t bytes, const char *what) -> int {
-      if (have >= bytes) return RT_OK;
-      // the last rt_multi_render synchronised every shard's stream and the
-      // root's before it returned: nothing still uses buf
-      scene_free(root, buf);
-      have = 0;
-      hipError_t e = scene_alloc(root, (void **)&buf, bytes);
-      if (e != hipSuccess) return set_err(RT_ERR_OOM, std::string("hipMalloc ") + what + ": " + hipGetErrorString(e));
-      have = bytes;
-      return RT_OK;
-    };
-    if ((rc = grow(m->stage, m->stage_bytes, std::max<size_t>(1, (size_t)n * stride * 64 * 3) * sizeof(double),
-                   "multi staging")))
+    // the last rt_multi_render synchronised every shard's stream and the
+    // root's before it returned: nothing still uses the two buffers
+    if ((rc = grow(root, m->stage, m->stage_bytes, std::max<size_t>(1, (size_t)n * stride * 64 * 3) * sizeof(double),
+                   Idle::Already, "hipMalloc multi staging")))
       return rc;
-    if ((rc = grow(m->frame, m->frame_bytes, std::max<size_t>(1, frame_d) * sizeof(double), "multi frame")))
+    if ((rc = grow(root, m->frame, m->frame_bytes, std::max<size_t>(1, frame_d) * sizeof(double), Idle::Already,
+                   "hipMalloc multi frame")))
       return rc;
   }
   std::vector<int> src(n, RT_OK);

@@ -40,6 +40,7 @@
 #include <hipcub/hipcub.hpp>
 #include <stdint.h>
 
+#include "rt_kernels.h"
 #include "rt_layout.h"
 
 namespace {

@@ -1,0 +1,65 @@
+// rt_kernels.h — every rtk_* launcher, declared once: included by the files
+// that define them (rt_kernel.hip, rt_frame.hip, rt_adaptive.hip,
+// rt_bvh_build.hip, rt_bvh_sah.hip) and by their caller (rt_api.cpp), so a
+// definition whose parameter list drifts from its callers' no longer compiles.
+#ifndef RT_KERNELS_H
+#define RT_KERNELS_H
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include "rt_layout.h"
+
+extern "C" {
+
+// ---- rt_kernel.hip: the render instances.  P carries its plan (rt_plan.h apply_plan)
+hipError_t rtk_launch_render(const DScene *S, const DCamera *C, const DLaunch *P, double *out,
+                             unsigned long long *stats, hipStream_t stream);
+size_t rtk_lds_bytes(int features, int stack_depth, int n_lds_nodes);
+hipError_t rtk_lds_plan(int features, int stack_depth, int lds_cap, RtkLdsPlan *plan);
+hipError_t rtk_lds_plan_pc(int features, int stack_depth, int force_waves, int *pcw, int64_t *free_bytes,
+                           int *blocks_per_cu);
+int rtk_lds_prims_enabled(void);
+int rtk_lds_perlin_enabled(void);
+int rtk_cost_f(int features);
+// RT_UNIT_TIMES builds only (tools/unit_timeline.py)
+hipError_t rtk_unit_times(unsigned long long *host, int n_units);
+hipError_t rtk_unit_times_clear(void);
+
+// ---- rt_frame.hip: frame assembly, tile exchange, dispatch order, bytes
+// after rtk_launch_render of a frame launch with chunked tiles: P->parts -> out
+hipError_t rtk_launch_split_sum(const DCamera *C, const DLaunch *P, double *out, hipStream_t stream);
+// after rtk_launch_render of a tile-layout launch: P->parts -> out[P->tile_order[tile]]
+hipError_t rtk_launch_shard_finish(const DLaunch *P, double *out, hipStream_t stream);
+hipError_t rtk_launch_tiles_sum(const double *parts, int64_t n_tiles, int chunks, double *out,
+                                hipStream_t stream);
+hipError_t rtk_launch_tile_order(const uint32_t *cost, int n, int n_head, int32_t *order, hipStream_t stream);
+hipError_t rtk_launch_tiles_to_frame(const double *tiles, int n_shards, int64_t shard_stride, int W,
+                                     int row_begin, int row_end, double scale, int scaled, int accumulate,
+                                     double *out, hipStream_t stream);
+hipError_t rtk_launch_to_bytes(const double *rgb, int64_t n, double scale, uint8_t *bytes, hipStream_t stream);
+
+// ---- rt_adaptive.hip: adaptive sampling
+hipError_t rtk_launch_tile_list_copy(const int32_t *in, int n, int tiles, int32_t *out, hipStream_t stream);
+hipError_t rtk_launch_adaptive_update(const double *delta, int batch_strata, const int32_t *list, int n_tiles,
+                                      int W, int H, double *acc, double *s1, double *s2, int32_t *tile_strata,
+                                      hipStream_t stream);
+hipError_t rtk_launch_adaptive_select(const double *s1, const double *s2, const int32_t *tile_strata,
+                                      int batch_strata, int W, int H, double threshold, double floor_,
+                                      int min_batches, const int32_t *list, int n_in, int32_t *out,
+                                      int32_t *count_out, double *tile_error, hipStream_t stream);
+hipError_t rtk_launch_to_bytes_tiles(const double *rgb, const int32_t *tile_strata, int W, int H, uint8_t *bytes,
+                                     hipStream_t stream);
+
+// ---- rt_bvh_build.hip, rt_bvh_sah.hip: the device BVH builders
+size_t rtk_lbvh_temp_bytes(int n);
+hipError_t rtk_build_lbvh(const double *boxes, const DItem *items_in, int n, const double *scene_lo,
+                          const double *scene_hi, DNode *nodes, DItem *items_out, int *depth_dev, void *temp,
+                          size_t temp_bytes, hipStream_t st);
+size_t rtk_sah_temp_bytes(int n);
+hipError_t rtk_build_sah(const double *boxes, const DItem *items_in, int n, DNode *nodes, DItem *items_out,
+                         void *temp, size_t temp_bytes, int stack_budget, int *n_nodes, int *depth,
+                         int *root_leaf, hipStream_t st);
+
+} // extern "C"
+#endif

@@ -15,6 +15,7 @@
 // (BVHNode.cpp:21-123) and each leaf carries the product of the 1/2 and 1/N
 // weights above it.
 #include "rt_scene.h"
+#include "rt_plan.h"
 
 #include <algorithm>
 #include <cmath>
@@ -1268,8 +1269,6 @@ int launch_geometry(const rt_frame *f, const rt_render_params *p, DLaunch &L, st
   if (chunks > L.sample_count && L.sample_count > 0)
     return bad(RT_ERR_INVALID, "strata_chunks exceeds the launched strata");
   if ((int64_t)L.n_local_tiles * chunks > 0x7FFFFFFF) return bad(RT_ERR_UNSUPPORTED, "too many work units");
-  L.n_chunks = chunks;
-  L.chunk_strata = (L.sample_count + chunks - 1) / chunks;
   L.unit_ctr = nullptr;
   L.grid_cap = 0;
   L.tile_order = nullptr;
@@ -1277,10 +1276,7 @@ int launch_geometry(const rt_frame *f, const rt_render_params *p, DLaunch &L, st
   // one chunk: every tile is a whole unit; strata_chunks > 1 (tile layout):
   // every tile split, its chunk partials are the caller's output (the launcher
   // points parts at the output buffer)
-  L.n_head = chunks > 1 ? 0 : L.n_local_tiles;
-  L.head_chunks = 1;
-  L.parts = nullptr;
-  L.parts_final = chunks > 1 ? 1 : 0;
+  apply_plan(L, chunks > 1 ? UnitPlan{0, 1, chunks} : whole_plan(L.n_local_tiles), nullptr, chunks > 1 ? 1 : 0);
   return RT_OK;
 }
 

@@ -108,7 +108,7 @@ def test_cli_gpus_shards_ppm_byte_identical(tmp_path):
 
 
 # Frames of more than 4 tiles per resident wave take the head/tail plan
-# (rt_api.cpp frame_plan): whole head tiles (<= 64 strata) or head tiles in a
+# (rt_plan.cpp frame_plan): whole head tiles (<= 64 strata) or head tiles in a
 # few chunks, the last tiles in 8x finer chunks.  rt_multi_render reproduces
 # the plan per shard, so the frame stays bit-identical; the plan only changes
 # the fp64 summation grouping against the uniform split (rt_tuning.tail_tiles < 0).

@@ -1,4 +1,4 @@
-"""strata_chunks = RT_CHUNKS_AUTO (rt_api.cpp subset_plan): a tile-subset launch
+"""strata_chunks = RT_CHUNKS_AUTO (rt_plan.cpp subset_plan): a tile-subset launch
 whose work units the library picks -- every tile in head chunks, the last
 tiles in finer tail chunks taken last, or the frame plan for subsets of more
 than 4 tiles per wave slot -- and whose output is the tiles' sums, the chunk

@@ -1,0 +1,37 @@
+#!/usr/bin/env python3
+"""Are the render_tiles instances of two `make asm` outputs the same code?
+python tools/isa_same.py A.s B.s  (the gfx950 .s files under build/asm/)
+
+Compares every render_tiles symbol's instruction text, without comments and
+assembler directives and with the function's number taken out of its
+.LBB<n>_ block labels (it shifts when other functions come or go).  Prints
+the number of symbols and of differing ones; exit 1 if a symbol differs or is
+in one file only."""
+import re
+import sys
+
+
+def functions(path):
+    out, name, body = {}, None, None
+    for line in open(path):
+        m = re.match(r"(\S*render_tiles\S*):", line)
+        if m and name is None:
+            name, body = m.group(1), []
+        elif name is not None:
+            if line.startswith(".Lfunc_end"):
+                out[name], name = body, None
+                continue
+            text = line.split(";")[0].rstrip()
+            if not text.strip() or re.match(r"\s+\.", text):  # comment / directive
+                continue
+            body.append(re.sub(r"\.LBB\d+_", ".LBB_", text))
+    return out
+
+
+a, b = functions(sys.argv[1]), functions(sys.argv[2])
+only = sorted(set(a) ^ set(b))
+differ = [k for k in sorted(set(a) & set(b)) if a[k] != b[k]]
+print("%d render_tiles symbols in A, %d in B, %d in one file only, %d differing" % (len(a), len(b), len(only), len(differ)))
+for k in only + differ:
+    print("  " + k)
+sys.exit(1 if only or differ or not a else 0)
