@@ -14,15 +14,18 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/rt_api.h"
 #include "rt_kernels.h"
 #include "rt_layout.h"
+#include "rt_lds_plan.h"
 #include "rt_plan.h"
 #include "rt_scene.h"
 
@@ -334,13 +337,15 @@ int rt_scene_create(const rt_scene_desc *desc, int32_t device, rt_scene **out) {
   return rt_scene_create_tuned(desc, device, nullptr, out);
 }
 
-int rt_scene_create_tuned(const rt_scene_desc *desc, int32_t device, const rt_tuning *tuning,
-                          rt_scene **out) {
-  if (!out) return set_err(RT_ERR_INVALID, "null output pointer");
-  *out = nullptr;
-  rt_tuning tune{};
-  if (tuning) tune = *tuning;
-  rtx::HostScene H;
+// ---- rt_scene_create_tuned, step by step.  The half-built scene belongs to a
+// ScenePtr: any early return destroys it.
+struct SceneDeleter {
+  void operator()(rt_scene *s) const { (void)rt_scene_destroy(s); }
+};
+using ScenePtr = std::unique_ptr<rt_scene, SceneDeleter>;
+
+static int compile_and_validate(const rt_scene_desc *desc, int32_t device, const rt_tuning &tune,
+                                rtx::HostScene &H) {
   H.sah_leaf_max = tune.sah_leaf_max;
   H.sah_leaf_split = tune.sah_leaf_split;
   H.sah_trav_x4 = tune.sah_trav_x4;
@@ -355,125 +360,81 @@ int rt_scene_create_tuned(const rt_scene_desc *desc, int32_t device, const rt_tu
   hipError_t e = hipGetDeviceCount(&ndev);
   if (e != hipSuccess) return hip_err(e, "hipGetDeviceCount");
   if (device < 0 || device >= ndev) return set_err(RT_ERR_INVALID, "device index out of range");
-  DeviceGuard g(device);
+  return RT_OK;
+}
 
-  // one allocation, 256-B aligned sub-ranges
-  struct Part {
-    const void *src;
-    size_t bytes;
-    size_t off;
+// One device allocation, 256-B aligned sub-ranges: the scene's tables
+// (rtx::for_each_table, in its order), then the STATS instance's counters and
+// the persistent launches' work-unit counter.
+struct BlockLayout {
+  std::vector<size_t> table_off;
+  size_t stats_off = 0, unit_ctr_off = 0, bytes = 0;
+};
+static BlockLayout layout_block(const rtx::HostScene &H, bool want4) {
+  BlockLayout L;
+  auto add = [&](size_t bytes) {
+    const size_t off = L.bytes;
+    L.bytes += align256(bytes ? bytes : 1);
+    return off;
   };
-  std::vector<Part> parts;
-  size_t off = 0;
-  auto add = [&](const void *src, size_t bytes, size_t reserve = 0) {
-    parts.push_back(Part{src, bytes, off});
-    reserve = std::max(reserve, bytes);
-    off += align256(reserve ? reserve : 1);
-    return parts.size() - 1;
-  };
-  // 4-wide world BVH (RT_FEAT_BVH4): asked for, or automatic from kBvh4Min
-  // primitives; collapsed from the binary tree once that exists (host or device
-  // build) into the node range, which is sized for it (<= one 4-wide node per
-  // binary node)
-  const int arity_req = desc->bvh_arity;
-  const bool want4 = arity_req == 4 || (arity_req == 0 && H.items.size() >= (size_t)rtx::kBvh4Min);
-  size_t iN = add(H.device_bvh ? nullptr : H.nodes.data(),
-                  H.device_bvh ? 0 : H.nodes.size() * sizeof(DNode),
-                  H.nodes.size() * (want4 ? sizeof(DNode4) : sizeof(DNode)));
-  size_t iI = add(H.items.data(), H.items.size() * sizeof(DItem));
-  size_t iB = add(H.bitems.data(), H.bitems.size() * sizeof(DItem));
-  size_t iMI = add(H.mitems.data(), H.mitems.size() * sizeof(DItem));
-  size_t iMB = add(H.mbox.data(), H.mbox.size() * sizeof(float));
-  size_t iX = add(H.xforms.data(), H.xforms.size() * sizeof(DXform));
-  size_t iS = add(H.spheres.data(), H.spheres.size() * sizeof(DSphere));
-  size_t iQ = add(H.quads.data(), H.quads.size() * sizeof(DQuad));
-  size_t iM = add(H.media.data(), H.media.size() * sizeof(DMedium));
-  size_t iMa = add(H.mats.data(), H.mats.size() * sizeof(DMat));
-  size_t iTx = add(H.texs.data(), H.texs.size() * sizeof(DTex));
-  size_t iP = add(H.perlin.data(), H.perlin.size() * sizeof(DPerlin));
-  size_t iLi = add(H.lights.data(), H.lights.size() * sizeof(DLight));
-  size_t iSt = add(nullptr, RT_N_STATS * sizeof(unsigned long long));
-  size_t iUc = add(nullptr, sizeof(int32_t));
+  rtx::for_each_table([&](auto, auto hm) {
+    using T = typename std::decay_t<decltype(H.*hm)>::value_type;
+    // the node range also takes the 4-wide collapse of the binary tree
+    // (RT_FEAT_BVH4; <= one 4-wide node per binary node)
+    const size_t each = std::is_same<T, DNode>::value && want4 ? sizeof(DNode4) : sizeof(T);
+    L.table_off.push_back(add((H.*hm).size() * each));
+  });
+  L.stats_off = add(RT_N_STATS * sizeof(unsigned long long));
+  L.unit_ctr_off = add(sizeof(int32_t));
+  return L;
+}
 
-  rt_scene *s = new rt_scene();
+// The scene's stream and events, its block, the tables uploaded into it and
+// bound to the DScene (the nodes of a device-built tree: the range only).
+static int open_scene(int32_t device, const rt_tuning &tune, const rtx::HostScene &H, const BlockLayout &L,
+                      ScenePtr &s) {
+  s.reset(new rt_scene());
   s->device = device;
   s->tune = tune;
-  s->block_bytes = off;
+  s->block_bytes = L.bytes;
+  hipError_t e;
   if ((e = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking)) != hipSuccess ||
       (e = hipEventCreate(&s->ev0)) != hipSuccess || (e = hipEventCreate(&s->ev1)) != hipSuccess ||
-      (e = hipEventCreateWithFlags(&s->last, hipEventDisableTiming)) != hipSuccess) {
-    rt_scene_destroy(s);
+      (e = hipEventCreateWithFlags(&s->last, hipEventDisableTiming)) != hipSuccess)
     return hip_err(e, "stream/event create");
-  }
-  e = scene_alloc(s, (void **)&s->block, off);
-  if (e != hipSuccess) {
-    rt_scene_destroy(s);
+  e = scene_alloc(s.get(), (void **)&s->block, L.bytes);
+  if (e != hipSuccess)
     return set_err(RT_ERR_OOM, std::string("hipMallocFromPoolAsync scene: ") + hipGetErrorString(e));
-  }
-  for (const Part &p : parts)
-    if (p.src && p.bytes) {
-      e = upload(s, s->block + p.off, p.src, p.bytes, hipMemcpyHostToDevice);
-      if (e != hipSuccess) {
-        rt_scene_destroy(s);
-        return hip_err(e, "upload scene");
-      }
-    }
-  auto P = [&](size_t i) { return (const void *)(s->block + parts[i].off); };
-  // with H.nodes holding the final binary tree: collapse and upload the 4-wide
-  // one -- kept binary when its stack would not fit RT_STACK_DEPTH4, or when
-  // its traversal stacks (three entries per 4-wide level, so a deep or lopsided
-  // collapse costs more LDS than the binary walk's one per level) would not fit
-  // the 4-wide instance's per-block LDS share at its occupancy target: LDS must
-  // never lower occupancy
-  auto collapse4 = [&](int features) -> hipError_t {
-    if (!want4 || H.root_is_leaf || H.nodes.empty()) return hipSuccess;
-    const int d4 = rtx::collapse_bvh4(H.nodes, H.nodes4);
-    RtkLdsPlan plan4{};
-    hipError_t fe = rtk_lds_plan(features | RT_FEAT_BVH4, rtx::bvh4_stack_depth(d4), tune.lds_cap, &plan4);
-    if (fe != hipSuccess) return fe;
-    if (rtx::bvh4_stack_depth(d4) > RT_STACK_DEPTH4 || !plan4.stack_fits) {
-      H.nodes4.clear();
-      return hipSuccess;
-    }
-    s->binary_cost = rtx::bvh_sah_cost(H.nodes);
-    H.bvh_arity = 4;
-    H.bvh_depth4 = d4;
-    return upload(s, (void *)P(iN), H.nodes4.data(), H.nodes4.size() * sizeof(DNode4),
-                  hipMemcpyHostToDevice);
-  };
+  size_t i = 0;
+  rtx::for_each_table([&](auto dm, auto hm) {
+    const auto &v = H.*hm;
+    using T = typename std::decay_t<decltype(v)>::value_type;
+    char *dst = s->block + L.table_off[i++];
+    s->ds.*dm = (const T *)dst;
+    const bool on_device = std::is_same<T, DNode>::value && H.device_bvh; // built there, below
+    if (e == hipSuccess && !v.empty() && !on_device)
+      e = upload(s.get(), dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
+  });
+  if (e != hipSuccess) return hip_err(e, "upload scene");
+  s->stats = (unsigned long long *)(s->block + L.stats_off);
+  s->unit_ctr = (int32_t *)(s->block + L.unit_ctr_off);
+  return RT_OK;
+}
+
+// The binary world tree: the host's (compile_scene), or built on the device
+// in place (rt_bvh_build.hip, rt_bvh_sah.hip) -- rebuilt on the host if the
+// device's is deeper than the traversal stack -- and downloaded if it is to be
+// collapsed.  Then the scene's counts and instance key (rtx::bind_counts).
+static int build_world_tree(rt_scene *s, rtx::HostScene &H, bool want4, int &builder) {
   DScene &d = s->ds;
-  d.nodes = (const DNode *)P(iN);
-  d.items = (const DItem *)P(iI);
-  d.bitems = (const DItem *)P(iB);
-  d.mitems = (const DItem *)P(iMI);
-  d.mbox = (const float *)P(iMB);
-  d.n_mitems = (int32_t)H.mitems.size();
-  d.xforms = (const DXform *)P(iX);
-  d.spheres = (const DSphere *)P(iS);
-  d.quads = (const DQuad *)P(iQ);
-  d.media = (const DMedium *)P(iM);
-  d.mats = (const DMat *)P(iMa);
-  d.texs = (const DTex *)P(iTx);
-  d.perlin = (const DPerlin *)P(iP);
-  d.lights = (const DLight *)P(iLi);
-  d.n_lights = (int32_t)H.lights.size();
-  d.n_nodes = (int32_t)H.nodes.size();
-  d.root_is_leaf = H.root_is_leaf;
-  d.n_root_items = H.n_root_items;
-  d.static_spheres = rtx::all_spheres_static(H);
-  d.features = rtx::scene_features(H);
-  d.features |= tune.extra_features & 15; // debug: widen the instance
-  // device-built world BVH (rt_bvh_build.hip), host SAH fallback if the linear
-  // tree is deeper than the traversal stack
-  int builder = RT_BVH_HOST;
+  DNode *nodes = const_cast<DNode *>(d.nodes);
+  DItem *items = const_cast<DItem *>(d.items);
+  builder = RT_BVH_HOST;
   if (H.device_bvh) {
     DeviceTree tree;
-    hipError_t be = device_bvh_build(s, H, (DNode *)P(iN), (DItem *)P(iI), tree);
-    if (be != hipSuccess) {
-      rt_scene_destroy(s);
-      return hip_err(be, "device BVH build");
-    }
-    const int max_depth = tune.lbvh_max_depth > 0 ? (int)tune.lbvh_max_depth : RT_STACK_DEPTH - 1;
+    hipError_t e = device_bvh_build(s, H, nodes, items, tree);
+    if (e != hipSuccess) return hip_err(e, "device BVH build");
+    const int max_depth = s->tune.lbvh_max_depth > 0 ? (int)s->tune.lbvh_max_depth : RT_STACK_DEPTH - 1;
     if (tree.depth >= 0 && tree.depth <= max_depth) {
       H.bvh_depth = tree.depth;
       H.nodes.resize(tree.n_nodes); // the device arrays hold the tree; sizes only
@@ -481,115 +442,92 @@ int rt_scene_create_tuned(const rt_scene_desc *desc, int32_t device, const rt_tu
       H.n_root_items = tree.root_leaf;
       builder = H.device_bvh;
       if (want4 && !H.root_is_leaf) { // the collapse runs on the host copy
-        hipError_t ce = upload(s, H.nodes.data(), P(iN), H.nodes.size() * sizeof(DNode),
-                               hipMemcpyDeviceToHost);
-        if (ce != hipSuccess) {
-          rt_scene_destroy(s);
-          return hip_err(ce, "BVH download");
-        }
+        e = upload(s, H.nodes.data(), nodes, H.nodes.size() * sizeof(DNode), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return hip_err(e, "BVH download");
       }
     } else { // too deep for the per-lane stack: rebuild on the host (depth-capped SAH)
       rtx::build_world_bvh_host(H);
-      hipError_t ue = upload(s, (void *)P(iN), H.nodes.data(), H.nodes.size() * sizeof(DNode),
-                             hipMemcpyHostToDevice);
-      if (ue == hipSuccess)
-        ue = upload(s, (void *)P(iI), H.items.data(), H.items.size() * sizeof(DItem),
-                    hipMemcpyHostToDevice);
-      if (ue != hipSuccess) {
-        rt_scene_destroy(s);
-        return hip_err(ue, "BVH upload");
-      }
-    }
-    d.n_nodes = (int32_t)H.nodes.size();
-    d.root_is_leaf = H.root_is_leaf;
-    d.n_root_items = H.n_root_items;
-  }
-  if ((e = collapse4(d.features)) != hipSuccess) {
-    rt_scene_destroy(s);
-    return hip_err(e, "4-wide BVH upload");
-  }
-  if (d.root_is_leaf) d.features |= RT_FEAT_FLAT;
-  // traversal stack: one entry per BVH level suffices (a pushed entry is the
-  // sibling of a node on the current root path; three per level for 4-wide
-  // nodes); LDS prefix of the BFS-ordered nodes sized to what the instance's
-  // occupancy leaves free
-  // the walk pushes without an overflow check (rt_path.h trace): the depth the
-  // host sizes the stack from must be the tree's, never clamped below it
-  if (H.bvh_depth + 1 > RT_STACK_DEPTH) {
-    rt_scene_destroy(s);
-    return set_err(RT_ERR_UNSUPPORTED, "world BVH deeper than the traversal stack (" +
-                                           std::to_string(H.bvh_depth) + " levels)");
-  }
-  d.stack_depth = std::max(1, H.bvh_depth + 1);
-  if (H.bvh_arity == 4) {
-    d.features |= RT_FEAT_BVH4;
-    d.n_nodes = (int32_t)H.nodes4.size();
-    d.stack_depth = rtx::bvh4_stack_depth(H.bvh_depth4);
-  }
-  RtkLdsPlan plan{};
-  {
-    int cus = 0;
-    hipError_t be = rtk_lds_plan(d.features, d.stack_depth, tune.lds_cap, &plan);
-    if (be == hipSuccess) be = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-    if (be != hipSuccess) {
-      rt_scene_destroy(s);
-      return set_err(RT_ERR_DEVICE, std::string("hipFuncGetAttributes: ") + hipGetErrorString(be));
-    }
-    s->wave_slots = cus * 4 * plan.waves_per_simd;
-    int budget = plan.n_nodes;
-    if (!plan.stack_fits) {
-      // the traversal stacks and static LDS exceed the block's share at the
-      // occupancy target (a compiler or register change can move that share):
-      // stage no nodes and accept fewer resident blocks per CU, as long as
-      // one block still fits the 64 KB a block may use without opt-in
-      if (plan.fixed_bytes > 64 * 1024) {
-        rt_scene_destroy(s);
-        return set_err(RT_ERR_UNSUPPORTED, "BVH traversal stacks exceed the per-block LDS limit");
-      }
-      std::fprintf(stderr,
-                   "rtx: traversal stacks need %d B of LDS per block, above the %d B share at %d "
-                   "waves/SIMD: no BVH nodes staged, lower occupancy\n",
-                   (int)plan.fixed_bytes, (int)plan.block_budget, (int)plan.waves_per_simd);
-      budget = 0;
-      s->wave_slots = cus * plan.resident_waves_per_cu;
-    }
-    if (tune.lds_nodes != 0) // A/B experiments, within the plan (< 0: none)
-      budget = std::max(0, std::min((int)tune.lds_nodes, plan.n_nodes));
-    d.n_lds_nodes = std::max(0, std::min(budget, d.n_nodes));
-    // the persistent instance: its node prefix, then -- if the whole tree is
-    // staged and room is left -- the world items and spheres (-1: no
-    // persistent launches)
-    int64_t pc_free = -1;
-    int pcw = 0;
-    int pc_bpc = 0;
-    be = rtk_lds_plan_pc(d.features, d.stack_depth, tune.pc_waves, &pcw, &pc_free, &pc_bpc);
-    d.pc_waves = pcw;
-    s->pc_grid = cus * pc_bpc;
-    if (be != hipSuccess) {
-      rt_scene_destroy(s);
-      return set_err(RT_ERR_DEVICE, std::string("hipFuncGetAttributes: ") + hipGetErrorString(be));
-    }
-    const int64_t node_b = RT_LDS_NODE_BYTES(d.features);
-    d.n_lds_nodes_pc = pc_free < 0 ? -1 : (int32_t)std::min<int64_t>(pc_free / node_b, d.n_nodes);
-    if (tune.lds_nodes_pc != 0 && d.n_lds_nodes_pc >= 0) // A/B experiments, within what the plan leaves free
-      d.n_lds_nodes_pc = (int32_t)std::max<int64_t>(
-          0, std::min<int64_t>({(int64_t)tune.lds_nodes_pc, d.n_nodes, pc_free / node_b}));
-    d.lds_items_pc = d.lds_spheres_pc = 0;
-    const int64_t prim_b = (int64_t)(H.items.size() * sizeof(DItem) + H.spheres.size() * sizeof(DSphere));
-    if (rtk_lds_prims_enabled() && !tune.no_lds_prims && pc_free >= 0 &&
-        d.n_lds_nodes_pc == d.n_nodes && pc_free - (int64_t)d.n_nodes * node_b >= prim_b &&
-        !H.items.empty()) {
-      d.lds_items_pc = (int32_t)H.items.size();
-      d.lds_spheres_pc = (int32_t)H.spheres.size();
+      e = upload(s, nodes, H.nodes.data(), H.nodes.size() * sizeof(DNode), hipMemcpyHostToDevice);
+      if (e == hipSuccess) e = upload(s, items, H.items.data(), H.items.size() * sizeof(DItem), hipMemcpyHostToDevice);
+      if (e != hipSuccess) return hip_err(e, "BVH upload");
     }
   }
-  // the one Perlin table of a noise scene in LDS (tune.no_lds_perlin: from
-  // HBM, A/B runs and the bit-identity test); several tables stay in HBM
-  d.lds_perlin = (d.features & RT_FEAT_NOISE) && H.perlin.size() == 1 && rtk_lds_perlin_enabled() &&
-                 !tune.no_lds_perlin;
-  s->stats = (unsigned long long *)(s->block + parts[iSt].off);
-  s->unit_ctr = (int32_t *)(s->block + parts[iUc].off);
+  rtx::bind_counts(d, H);
+  d.features |= s->tune.extra_features & 15; // debug: widen the instance
+  return RT_OK;
+}
 
+// 4-wide world BVH (RT_FEAT_BVH4; want4: asked for, or automatic from
+// kBvh4Min primitives): with H.nodes holding the final binary tree, collapse
+// it and upload the 4-wide one over the node range -- or keep the binary one
+// (collapse4_verdict, rt_lds_plan.h).
+static int collapse_world_tree(rt_scene *s, rtx::HostScene &H, bool want4) {
+  if (!want4 || H.root_is_leaf || H.nodes.empty()) return RT_OK;
+  DScene &d = s->ds;
+  const int d4 = rtx::collapse_bvh4(H.nodes, H.nodes4);
+  KernelAttrs a4;
+  hipError_t e = rtk_instance_attrs(d.features | RT_FEAT_BVH4, 0, &a4);
+  if (e != hipSuccess) return hip_err(e, "4-wide BVH upload");
+  if (collapse4_verdict(a4, d.features, d4, s->tune.lds_cap) != COLLAPSE4_FITS) {
+    H.nodes4.clear();
+    return RT_OK;
+  }
+  s->binary_cost = rtx::bvh_sah_cost(H.nodes);
+  H.bvh_arity = 4;
+  H.bvh_depth4 = d4;
+  e = upload(s, const_cast<DNode *>(d.nodes), H.nodes4.data(), H.nodes4.size() * sizeof(DNode4),
+             hipMemcpyHostToDevice);
+  if (e != hipSuccess) return hip_err(e, "4-wide BVH upload");
+  d.features |= RT_FEAT_BVH4;
+  d.n_nodes = (int32_t)H.nodes4.size();
+  return RT_OK;
+}
+
+// The traversal stack and what the scene's blocks keep in LDS: the attributes
+// of the instances the scene runs and the device's CU count into the residency
+// plan (rt_lds_plan.h), its outcome into the DScene and the wave-slot counts.
+static int apply_residency(rt_scene *s, const rtx::HostScene &H, RtkLdsPlan &plan) {
+  DScene &d = s->ds;
+  std::string err;
+  d.stack_depth = rtx::traversal_stack_depth(H, err);
+  if (!d.stack_depth) return set_err(RT_ERR_UNSUPPORTED, err);
+  LdsPlanInput in{};
+  hipError_t e = rtk_instance_attrs(d.features, 0, &in.render);
+  if (e == hipSuccess) e = hipDeviceGetAttribute(&in.cus, hipDeviceAttributeMultiprocessorCount, s->device);
+  if (RT_PERSIST_F((unsigned)d.features & 63u)) {
+    if (e == hipSuccess) e = rtk_instance_attrs(d.features, kPcWaves, &in.pc16);
+    if (e == hipSuccess) e = rtk_instance_attrs(d.features, kWaves, &in.pc4);
+  }
+  // (a failed CU-count query is reported under the same name, as it always was)
+  if (e != hipSuccess) return set_err(RT_ERR_DEVICE, std::string("hipFuncGetAttributes: ") + hipGetErrorString(e));
+  in.features = d.features;
+  in.stack_depth = d.stack_depth;
+  in.n_nodes = d.n_nodes;
+  in.n_items = (int32_t)H.items.size();
+  in.n_spheres = (int32_t)H.spheres.size();
+  in.n_perlin = (int32_t)H.perlin.size();
+  const SceneLdsPlan p = plan_scene_lds(in, s->tune);
+  plan = p.render;
+  if (p.outcome == LDS_UNSUPPORTED)
+    return set_err(RT_ERR_UNSUPPORTED, "BVH traversal stacks exceed the per-block LDS limit");
+  if (p.outcome == LDS_STACKS_OVER_SHARE)
+    std::fprintf(stderr,
+                 "rtx: traversal stacks need %d B of LDS per block, above the %d B share at %d "
+                 "waves/SIMD: no BVH nodes staged, lower occupancy\n",
+                 (int)plan.fixed_bytes, (int)plan.block_budget, (int)plan.waves_per_simd);
+  s->wave_slots = p.wave_slots;
+  s->pc_grid = p.pc_grid;
+  d.n_lds_nodes = p.n_lds_nodes;
+  d.pc_waves = p.pc_waves;
+  d.n_lds_nodes_pc = p.n_lds_nodes_pc;
+  d.lds_items_pc = p.lds_items_pc;
+  d.lds_spheres_pc = p.lds_spheres_pc;
+  d.lds_perlin = p.lds_perlin;
+  return RT_OK;
+}
+
+static void fill_info(rt_scene *s, const rtx::HostScene &H, const RtkLdsPlan &plan, int builder) {
+  const DScene &d = s->ds;
   rt_scene_info &in = s->info;
   std::memset(&in, 0, sizeof in);
   in.n_nodes = d.n_nodes;
@@ -602,7 +540,7 @@ int rt_scene_create_tuned(const rt_scene_desc *desc, int32_t device, const rt_tu
   in.node_bytes = (int32_t)(H.bvh_arity == 4 ? sizeof(DNode4) : sizeof(DNode));
   in.sphere_bytes = (int32_t)sizeof(DSphere);
   in.quad_bytes = (int32_t)sizeof(DQuad);
-  in.device_bytes = (int64_t)off;
+  in.device_bytes = (int64_t)s->block_bytes;
   in.features = d.features;
   in.lds_nodes = d.n_lds_nodes;
   in.bvh_builder = builder;
@@ -616,7 +554,29 @@ int rt_scene_create_tuned(const rt_scene_desc *desc, int32_t device, const rt_tu
   in.persistent_block_waves = d.pc_waves;
   in.lds_perlin = d.lds_perlin;
   in.lds_node_bytes = RT_LDS_NODE_BYTES(d.features);
-  *out = s;
+}
+
+int rt_scene_create_tuned(const rt_scene_desc *desc, int32_t device, const rt_tuning *tuning,
+                          rt_scene **out) {
+  if (!out) return set_err(RT_ERR_INVALID, "null output pointer");
+  *out = nullptr;
+  rt_tuning tune{};
+  if (tuning) tune = *tuning;
+  rtx::HostScene H;
+  int rc = compile_and_validate(desc, device, tune, H);
+  if (rc != RT_OK) return rc;
+  DeviceGuard g(device);
+  const bool want4 = desc->bvh_arity == 4 || (desc->bvh_arity == 0 && H.items.size() >= (size_t)rtx::kBvh4Min);
+  ScenePtr s;
+  int builder = RT_BVH_HOST;
+  RtkLdsPlan plan{};
+  rc = open_scene(device, tune, H, layout_block(H, want4), s);
+  if (rc == RT_OK) rc = build_world_tree(s.get(), H, want4, builder);
+  if (rc == RT_OK) rc = collapse_world_tree(s.get(), H, want4);
+  if (rc == RT_OK) rc = apply_residency(s.get(), H, plan);
+  if (rc != RT_OK) return rc;
+  fill_info(s.get(), H, plan, builder);
+  *out = s.release();
   return RT_OK;
 }
 

@@ -36,6 +36,7 @@
 #include <utility>
 
 #include "rt_kernels.h"
+#include "rt_lds_plan.h"
 #include "rt_path.h"
 #include "rt_plan.h"
 
@@ -45,32 +46,10 @@ using namespace rtp;
 // Idle lanes that trigger a refill while other lanes still trace (measured:
 // 16 for the plain instance, C3 +4 %; the rich instances lose with any delay).
 #define RT_REGEN_MIN(F) ((F) == F_FLAT ? 16 : (((F) & ~F_BVH4) == 0 ? 16 : 1))
-constexpr int kWaves = 4; // waves (work units) per block
-// Flat instances (no BVH, nothing staged in LDS) run one-wave blocks: a
-// block's wave slots are released only when all of its waves have ended, so
-// with 4-wave blocks a slot idles until the slowest unit of its block is done
-// (measured: C2 +2.0 %, C4 +10.4 % over 4-wave blocks; 2-wave blocks +0.5 % /
-// +6.3 %; profiles/r03g_ab.log).  BVH instances keep 4-wave blocks: their
-// waves share the block's staged BVH prefix.
-constexpr int block_waves(unsigned f) { return (f & F_FLAT) ? 1 : kWaves; }
-// Waves per block of the persistent instance: one block per CU (16 = 4 SIMDs x
-// its 4-waves/SIMD target), so the CU's 160 KB of LDS holds ONE copy of the
-// staged BVH beside its 16 waves' stacks instead of four copies for four
-// 4-wave blocks (gfx950: a workgroup may own all 160 KB).
-constexpr int kPcWaves = RT_PC_WAVES; // rt_layout.h
-// the persistent instance also stages the world items and spheres when they fit
-constexpr size_t kLdsPerCu = 160 * 1024;
-
 // Occupancy target per instance (waves per SIMD): the compiler may spill a few
 // registers to reach it.  Measured: 4 for the plain instance (C3
 // +12 % over 3), 3 for the rich ones (C4 +8.6 % over the 2 that 224 VGPRs give).
 #define RT_WAVES_PER_EU(F) ((F) == F_FLAT ? 4 : (((F) & ~F_BVH4) == 0 ? 4 : 3))
-// Feature sets with a persistent chunked-frame instance (render_tiles<.., PC>,
-// whose waves pull work units from a counter): the plain BVH walks (C3 +3.4 %,
-// profiles/r02ab-af_*); the flat and the rich instances keep one unit per wave
-// -- the unit loop's extra live state cost them 2-20 %.
-#define RT_PERSIST_F(F) (((F) & ~F_BVH4) == 0)
-
 // The launch fields read afresh from the kernarg segment at each work unit
 // (FRESH, the persistent instances): the asm hides the segment pointer's
 // value, so the loads stay inside the unit loop instead of being hoisted out
@@ -249,7 +228,7 @@ __global__ __launch_bounds__(64 * (PCW ? PCW : block_waves(F))) __attribute__((a
   DScene S = S_;
   if constexpr (PC) S.n_lds_nodes = S_.n_lds_nodes_pc;
   // dynamic LDS: traversal stacks [BW][S.stack_depth][64] ints, then the
-  // staged BVH prefix nodes [0, S.n_lds_nodes) (sizes: rtk_lds_bytes)
+  // staged BVH prefix nodes [0, S.n_lds_nodes) (sizes: rt_lds_plan.h lds_bytes)
   extern __shared__ int4 dyn_lds[];
   __shared__ double acc_lds[BW][64][3];
   // compacted leaf tests (BVH instances only; 1 KB per wave)
@@ -556,84 +535,20 @@ const RenderFn *render_table(bool stats) {
 } // namespace
 
 // ---------------------------------------------------------------- launchers
-extern "C" size_t rtk_lds_bytes(int features, int stack_depth, int n_lds_nodes) {
-  const size_t node = RT_LDS_NODE_BYTES(features);
-  return (size_t)block_waves((unsigned)features) * stack_depth * 64 * sizeof(int) +
-         (size_t)n_lds_nodes * node;
-}
-// a persistent instance's dynamic LDS (pcw waves per block)
-static size_t lds_bytes_pc(int features, int pcw, int stack_depth, int n_lds_nodes) {
-  const size_t node = RT_LDS_NODE_BYTES(features);
-  return (size_t)pcw * stack_depth * 64 * sizeof(int) + (size_t)n_lds_nodes * node;
-}
-
-// LDS plan per block at the occupancy the instance's register count allows
-// (blocks of kWaves waves over the 4 SIMDs): the bytes left for the staged BVH
-// prefix after the static LDS and the traversal stacks, and whether those two
-// fit at all (the caller then keeps a shallower tree).  lds_cap > 0 lowers the
-// per-block cap (rt_tuning.lds_cap: tests of that fallback).
-extern "C" hipError_t rtk_lds_plan(int features, int stack_depth, int lds_cap, RtkLdsPlan *plan) {
-  hipFuncAttributes a;
-  hipError_t e = hipFuncGetAttributes(&a, reinterpret_cast<const void *>(render_table(false)[features & F_ALL]));
-  if (e != hipSuccess) return e;
-  const int regs = ((a.numRegs + 7) / 8) * 8;
-  int waves_per_simd = regs > 0 ? 512 / regs : 8;
-  if (waves_per_simd > 8) waves_per_simd = 8;
-  if (waves_per_simd < 1) waves_per_simd = 1;
-  size_t lds_cu = 160 * 1024, cap = 64 * 1024; // per CU; per block without opt-in
-  if (lds_cap > 0 && (size_t)lds_cap < cap) cap = (size_t)lds_cap;
-  const int bw = block_waves((unsigned)features);
-  const int blocks_per_cu = waves_per_simd * 4 / bw > 0 ? waves_per_simd * 4 / bw : 1;
-  size_t per_block = lds_cu / blocks_per_cu;
-  if (per_block > cap) per_block = cap;
-  const size_t fixed = a.sharedSizeBytes + rtk_lds_bytes(features, stack_depth, 0);
-  const size_t node = RT_LDS_NODE_BYTES(features);
-  plan->waves_per_simd = waves_per_simd;
-  plan->block_budget = (int32_t)per_block;
-  plan->fixed_bytes = (int32_t)fixed;
-  plan->stack_fits = fixed <= per_block;
-  plan->n_nodes = per_block > fixed ? (int)((per_block - fixed) / node) : 0;
-  // stacks over the share: fewer blocks per CU (the host then stages no nodes)
-  const int lds_blocks = fixed > 0 ? (int)(lds_cu / fixed) : blocks_per_cu;
-  plan->resident_waves_per_cu = std::min(blocks_per_cu, std::max(1, lds_blocks)) * bw;
-  return hipSuccess;
-}
-
-// The persistent instance a scene uses and the LDS it has left for staging
-// after its stacks and static LDS: blocks of kPcWaves waves (one per CU, which
-// may own the CU's whole LDS) if their stacks fit, else blocks of kWaves waves
-// (one per SIMD at the occupancy target: a quarter of the CU's LDS each);
-// *pcw = 0 / *free_bytes = -1 when neither fits or the feature set has no
-// persistent instance.
-extern "C" hipError_t rtk_lds_plan_pc(int features, int stack_depth, int force_waves, int *pcw,
-                                      int64_t *free_bytes,
-                                      int *blocks_per_cu) {
-  *free_bytes = -1;
-  *pcw = 0;
-  *blocks_per_cu = 0;
+// What the runtime reports about the instance a scene of these features runs:
+// the one-unit instance (pc_waves 0), or the persistent instance in blocks of
+// pc_waves waves (RT_PERSIST_F feature sets) -- the inputs of the residency
+// plan (rt_lds_plan.h).
+extern "C" hipError_t rtk_instance_attrs(int features, int pc_waves, KernelAttrs *attrs) {
   const unsigned f = (unsigned)(features & F_ALL);
-  if (!RT_PERSIST_F(f)) return hipSuccess;
-  for (int w : {kPcWaves, kWaves}) { // force_waves == kWaves (tests): the 4-wave form on any scene
-    if (force_waves == kWaves && w != kWaves) continue;
-    hipFuncAttributes a;
-    hipError_t e = hipFuncGetAttributes(&a, reinterpret_cast<const void *>(persistent_instance(f, w)));
-    if (e != hipSuccess) return e;
-    const int regs = ((a.numRegs + 7) / 8) * 8;
-    const int waves_per_simd = std::max(1, std::min(8, regs > 0 ? 512 / regs : 8));
-    const int bpc = std::max(1, waves_per_simd * 4 / w); // resident blocks per CU
-    const size_t per_block = kLdsPerCu / bpc;
-    const size_t fixed = a.sharedSizeBytes + lds_bytes_pc(features, w, stack_depth, 0);
-    if (fixed <= per_block) {
-      *pcw = w;
-      *blocks_per_cu = bpc;
-      *free_bytes = (int64_t)(per_block - fixed);
-      return hipSuccess;
-    }
-  }
+  hipFuncAttributes a;
+  hipError_t e = hipFuncGetAttributes(
+      &a, reinterpret_cast<const void *>(pc_waves ? persistent_instance(f, pc_waves) : render_table(false)[f]));
+  if (e != hipSuccess) return e;
+  attrs->num_regs = a.numRegs;
+  attrs->static_lds = (int32_t)a.sharedSizeBytes;
   return hipSuccess;
 }
-extern "C" int rtk_lds_prims_enabled(void) { return 1; }
-extern "C" int rtk_lds_perlin_enabled(void) { return 1; }
 
 // Lets a persistent instance's blocks use more than 64 KB of dynamic LDS: set
 // once per device and function, to the most any scene's plan can ask for (the
@@ -672,7 +587,7 @@ extern "C" hipError_t rtk_launch_render(const DScene *S, const DCamera *C, const
     fn = cost_instance((unsigned)(S->features & F_ALL));
     if (fn == nullptr) return hipErrorInvalidValue;
   }
-  size_t lds = rtk_lds_bytes(S->features, S->stack_depth, S->n_lds_nodes);
+  size_t lds = lds_bytes(S->features, S->stack_depth, S->n_lds_nodes);
   int launch_waves = bw;
   DLaunch Q = *P;
   const unsigned f = (unsigned)(S->features & F_ALL);
@@ -683,8 +598,7 @@ extern "C" hipError_t rtk_launch_render(const DScene *S, const DCamera *C, const
     fn = persistent_instance(f, S->pc_waves);
     blocks = Q.grid_cap;
     launch_waves = S->pc_waves;
-    lds = lds_bytes_pc(S->features, S->pc_waves, S->stack_depth, S->n_lds_nodes_pc) +
-          (size_t)S->lds_items_pc * sizeof(DItem) + (size_t)S->lds_spheres_pc * sizeof(DSphere);
+    lds = lds_bytes_pc(S->features, S->pc_waves, S->stack_depth, S->n_lds_nodes_pc, S->lds_items_pc, S->lds_spheres_pc);
     hipError_t e = allow_cu_lds(fn);
     if (e != hipSuccess) return e;
     e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(Q.unit_ctr), blocks * S->pc_waves, 1, stream);

@@ -9,18 +9,16 @@
 #include <stdint.h>
 
 #include "rt_layout.h"
+#include "rt_lds_plan.h"
 
 extern "C" {
 
 // ---- rt_kernel.hip: the render instances.  P carries its plan (rt_plan.h apply_plan)
 hipError_t rtk_launch_render(const DScene *S, const DCamera *C, const DLaunch *P, double *out,
                              unsigned long long *stats, hipStream_t stream);
-size_t rtk_lds_bytes(int features, int stack_depth, int n_lds_nodes);
-hipError_t rtk_lds_plan(int features, int stack_depth, int lds_cap, RtkLdsPlan *plan);
-hipError_t rtk_lds_plan_pc(int features, int stack_depth, int force_waves, int *pcw, int64_t *free_bytes,
-                           int *blocks_per_cu);
-int rtk_lds_prims_enabled(void);
-int rtk_lds_perlin_enabled(void);
+// the residency plan's inputs (rt_lds_plan.h): the one-unit instance of a
+// feature set (pc_waves 0) or its persistent instance in blocks of pc_waves waves
+hipError_t rtk_instance_attrs(int features, int pc_waves, KernelAttrs *attrs);
 int rtk_cost_f(int features);
 // RT_UNIT_TIMES builds only (tools/unit_timeline.py)
 hipError_t rtk_unit_times(unsigned long long *host, int n_units);

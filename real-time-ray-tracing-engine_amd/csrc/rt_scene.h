@@ -70,6 +70,50 @@ inline int32_t scene_features(const HostScene &H) {
   return f;
 }
 
+// The scene's tables, named once: f(DScene member, HostScene vector) for each,
+// in the order the GPU library lays them out in a scene's device block
+// (rt_api.cpp).  A table added to DScene is added here and nowhere else.
+template <class F>
+inline void for_each_table(F &&f) {
+  f(&DScene::nodes, &HostScene::nodes);
+  f(&DScene::items, &HostScene::items);
+  f(&DScene::bitems, &HostScene::bitems);
+  f(&DScene::mitems, &HostScene::mitems);
+  f(&DScene::mbox, &HostScene::mbox);
+  f(&DScene::xforms, &HostScene::xforms);
+  f(&DScene::spheres, &HostScene::spheres);
+  f(&DScene::quads, &HostScene::quads);
+  f(&DScene::media, &HostScene::media);
+  f(&DScene::mats, &HostScene::mats);
+  f(&DScene::texs, &HostScene::texs);
+  f(&DScene::perlin, &HostScene::perlin);
+  f(&DScene::lights, &HostScene::lights);
+}
+
+// What a DScene holds of a compiled scene beside its tables: the counts, the
+// binary world tree's shape and the instance key (RT_FEAT_FLAT from
+// root_is_leaf).  The GPU library calls it once the world tree is final.
+inline void bind_counts(DScene &S, const HostScene &H) {
+  S.n_mitems = (int32_t)H.mitems.size();
+  S.n_lights = (int32_t)H.lights.size();
+  S.n_nodes = (int32_t)H.nodes.size();
+  S.root_is_leaf = H.root_is_leaf;
+  S.n_root_items = H.n_root_items;
+  S.static_spheres = all_spheres_static(H);
+  S.features = scene_features(H) | (H.root_is_leaf ? RT_FEAT_FLAT : 0);
+}
+
+// The host binder: a DScene over the HostScene's own vectors (the CPU
+// backend, host/rtx_cpu.cpp; the kernel-source emulator, tests/native/
+// rt_emulate.cpp, which then points `nodes` at the 4-wide collapse).  The LDS
+// fields stay 0; stack_depth is the caller's (traversal_stack_depth).
+inline DScene bind_host_scene(const HostScene &H) {
+  DScene S{};
+  for_each_table([&](auto dm, auto hm) { S.*dm = (H.*hm).data(); });
+  bind_counts(S, H);
+  return S;
+}
+
 // Scenes with at least this many world primitives build their BVH on the
 // device when rt_scene_desc.bvh_builder is RT_BVH_AUTO.
 constexpr int kDeviceBuildMin = 65536;
@@ -96,6 +140,26 @@ double bvh_sah_cost(const std::vector<DNode> &nodes);
 // The traversal stack a 4-wide walk of depth4 levels needs: at most three
 // pushed siblings per level on the current root path.
 inline int bvh4_stack_depth(int depth4) { return 3 * depth4 + 1; }
+
+// The per-lane traversal stack of the tree a scene walks (DScene::stack_depth):
+// one entry per BVH level suffices (a pushed entry is the sibling of a node on
+// the current root path; bvh4_stack_depth for a 4-wide tree, bvh_arity 4).
+// The walk pushes without an overflow check (rt_path.h trace), so the depth the
+// stack is sized from must be the tree's, never clamped below it: a tree
+// deeper than RT_STACK_DEPTH / RT_STACK_DEPTH4 is refused -- returns 0 with
+// `err` filled.
+inline int traversal_stack_depth(const HostScene &H, std::string &err) {
+  if (H.bvh_depth + 1 > RT_STACK_DEPTH) {
+    err = "world BVH deeper than the traversal stack (" + std::to_string(H.bvh_depth) + " levels)";
+    return 0;
+  }
+  if (H.bvh_arity != 4) return H.bvh_depth + 1 > 1 ? H.bvh_depth + 1 : 1;
+  if (bvh4_stack_depth(H.bvh_depth4) > RT_STACK_DEPTH4) {
+    err = "4-wide world BVH deeper than the traversal stack (" + std::to_string(H.bvh_depth4) + " levels)";
+    return 0;
+  }
+  return bvh4_stack_depth(H.bvh_depth4);
+}
 
 // Returns RT_OK or an error code with `err` filled.
 int compile_scene(const rt_scene_desc *desc, HostScene &out, std::string &err);

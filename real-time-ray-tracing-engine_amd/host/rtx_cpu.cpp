@@ -117,32 +117,9 @@ int rt_cpu_render(const rt_scene_desc *desc, const rt_frame *f, const rt_render_
   rc = rtx::compile_scene(desc, H, err);
   if (rc != RT_OK) return fail(rc, err);
   if (H.device_bvh) rtx::build_world_bvh_host(H); // the device builders are the GPU library's
-  const int stack_depth = std::max(1, H.bvh_depth + 1);
-  if (stack_depth > RT_STACK_DEPTH)
-    return fail(RT_ERR_UNSUPPORTED, "world BVH deeper than the traversal stack (" +
-                                        std::to_string(H.bvh_depth) + " levels)");
-  DScene S{};
-  S.nodes = H.nodes.data();
-  S.items = H.items.data();
-  S.bitems = H.bitems.data();
-  S.mitems = H.mitems.data();
-  S.mbox = H.mbox.data();
-  S.n_mitems = (int32_t)H.mitems.size();
-  S.xforms = H.xforms.data();
-  S.spheres = H.spheres.data();
-  S.quads = H.quads.data();
-  S.media = H.media.data();
-  S.mats = H.mats.data();
-  S.texs = H.texs.data();
-  S.perlin = H.perlin.data();
-  S.lights = H.lights.data();
-  S.n_lights = (int32_t)H.lights.size();
-  S.n_nodes = (int32_t)H.nodes.size();
-  S.root_is_leaf = H.root_is_leaf;
-  S.n_root_items = H.n_root_items;
-  S.features = rtx::scene_features(H) | (H.root_is_leaf ? F_FLAT : 0);
-  S.static_spheres = rtx::all_spheres_static(H);
-  S.stack_depth = stack_depth;
+  DScene S = rtx::bind_host_scene(H);
+  S.stack_depth = rtx::traversal_stack_depth(H, err);
+  if (!S.stack_depth) return fail(RT_ERR_UNSUPPORTED, err);
   S.n_lds_nodes = S.n_nodes; // the walk reads every node from `lnodes`, in the staged form
   std::vector<DNodeL> lnodes_l;
   const DNode *lnodes = S.nodes;

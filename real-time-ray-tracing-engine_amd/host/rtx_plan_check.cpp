@@ -1,10 +1,15 @@
 // rtx_plan_check — host-only check of the work-unit plans (csrc/rt_plan.h,
-// csrc/rt_plan.cpp; no HIP).
+// csrc/rt_plan.cpp) and of the LDS residency plan (csrc/rt_lds_plan.h,
+// csrc/rt_lds_plan.cpp); no HIP.
 //   rtx_plan_check          sweeps launches, devices and tunings and checks the
 //                           unit arithmetic's invariants on every plan the
-//                           planners return; exit 1 at the first violation
+//                           planners return; then sweeps kernel attributes,
+//                           scene sizes and tunings and checks the residency
+//                           plans' invariants; exit 1 at the first violation
 //   rtx_plan_check --table  prints the plans of the pinned cases, one per line
 //                           (tests/test_plan.py compares them with its table)
+//   rtx_plan_check --lds-table  the same for the residency plans
+//                           (tests/test_lds_plan.py)
 #include <cstdio>
 #include <cstring>
 #include <set>
@@ -12,6 +17,7 @@
 #include <tuple>
 #include <vector>
 
+#include "../csrc/rt_lds_plan.h"
 #include "../csrc/rt_plan.h"
 
 namespace {
@@ -268,13 +274,221 @@ int table() {
   return 0;
 }
 
+// ---- the LDS residency plan (csrc/rt_lds_plan.h)
+
+rt_tuning lds_tuning(int lds_cap, int lds_nodes, int lds_nodes_pc, int no_lds_prims, int pc_waves,
+                     int no_lds_perlin) {
+  rt_tuning t;
+  std::memset(&t, 0, sizeof t);
+  t.lds_cap = lds_cap;
+  t.lds_nodes = lds_nodes;
+  t.lds_nodes_pc = lds_nodes_pc;
+  t.no_lds_prims = no_lds_prims;
+  t.pc_waves = pc_waves;
+  t.no_lds_perlin = no_lds_perlin;
+  return t;
+}
+// every field the plan reads at zero (default), positive and negative where
+// that means something; the values the GPU tests pass
+const Tune kLdsTunes[] = {
+    {"default", lds_tuning(0, 0, 0, 0, 0, 0)},
+    {"lds_cap=4096", lds_tuning(4096, 0, 0, 0, 0, 0)},      // test_bvh4
+    {"lds_cap=30000", lds_tuning(30000, 0, 0, 0, 0, 0)},
+    {"lds_cap=100000", lds_tuning(100000, 0, 0, 0, 0, 0)},  // above 64 KB: no effect
+    {"lds_nodes=100", lds_tuning(0, 100, 0, 0, 0, 0)},
+    {"lds_nodes=-1", lds_tuning(0, -1, 0, 0, 0, 0)},        // test_hit_identity
+    {"lds_nodes_pc=100", lds_tuning(0, 0, 100, 0, 0, 0)},
+    {"lds_nodes_pc=-1", lds_tuning(0, 0, -1, 0, 0, 0)},     // test_persistent
+    {"no_lds_prims", lds_tuning(0, 0, 0, 1, 0, 0)},         // test_persistent
+    {"pc_waves=4", lds_tuning(0, 0, 0, 0, 4, 0)},           // test_persistent
+    {"no_lds_perlin", lds_tuning(0, 0, 0, 0, 0, 1)},        // test_lds_perlin
+    {"lds_cap=4096 lds_nodes=100 pc_waves=4", lds_tuning(4096, 100, 0, 0, 4, 0)},
+};
+
+#define LDS_REQUIRE(cond)                                                                          \
+  do {                                                                                             \
+    if (!(cond)) {                                                                                 \
+      why = #cond;                                                                                 \
+      return false;                                                                                \
+    }                                                                                              \
+  } while (0)
+
+// What must hold of every residency plan: nothing staged beyond the LDS the
+// occupancy target leaves, and the dynamic LDS the launcher requests
+// (lds_bytes / lds_bytes_pc of the DScene fields) is what the planner budgeted.
+bool check_lds_plan(const LdsPlanInput &in, const SceneLdsPlan &p, std::string &why) {
+  const RtkLdsPlan &r = p.render;
+  const int64_t node_b = RT_LDS_NODE_BYTES(in.features);
+  LDS_REQUIRE(r.waves_per_simd >= 1 && r.waves_per_simd <= 8);
+  LDS_REQUIRE(r.block_budget > 0 && (size_t)r.block_budget <= kLdsPerBlock);
+  LDS_REQUIRE(r.stack_fits == (r.fixed_bytes <= r.block_budget));
+  LDS_REQUIRE((size_t)r.fixed_bytes == in.render.static_lds + lds_bytes(in.features, in.stack_depth, 0));
+  if (p.outcome == LDS_UNSUPPORTED) {
+    LDS_REQUIRE(!r.stack_fits && (size_t)r.fixed_bytes > kLdsPerBlock);
+    return true;
+  }
+  LDS_REQUIRE((p.outcome == LDS_OK) == (r.stack_fits != 0));
+  LDS_REQUIRE((size_t)r.fixed_bytes <= kLdsPerBlock);
+  LDS_REQUIRE(p.n_lds_nodes >= 0 && p.n_lds_nodes <= in.n_nodes);
+  const size_t launch = in.render.static_lds + lds_bytes(in.features, in.stack_depth, p.n_lds_nodes);
+  LDS_REQUIRE(launch == (size_t)(r.fixed_bytes + p.n_lds_nodes * node_b));
+  if (r.stack_fits) LDS_REQUIRE(launch <= (size_t)r.block_budget);
+  else LDS_REQUIRE(p.n_lds_nodes == 0);
+  LDS_REQUIRE(p.wave_slots > 0 && p.wave_slots % in.cus == 0);
+  // as many blocks as the slots count fit the CU's LDS
+  const int bw = block_waves((unsigned)in.features);
+  LDS_REQUIRE(p.wave_slots / in.cus % bw == 0 && (size_t)(p.wave_slots / in.cus / bw) * launch <= kLdsPerCu);
+  LDS_REQUIRE((p.n_lds_nodes_pc == -1) == (p.pc_waves == 0));
+  if (p.pc_waves == 0) {
+    LDS_REQUIRE(p.pc_grid == 0 && p.lds_items_pc == 0 && p.lds_spheres_pc == 0);
+  } else {
+    LDS_REQUIRE(p.pc_waves == kPcWaves || p.pc_waves == kWaves);
+    LDS_REQUIRE(RT_PERSIST_F((unsigned)in.features & 63u));
+    LDS_REQUIRE(p.pc_grid > 0 && p.pc_grid % in.cus == 0);
+    LDS_REQUIRE(p.n_lds_nodes_pc >= 0 && p.n_lds_nodes_pc <= in.n_nodes);
+    const KernelAttrs a = p.pc_waves == kPcWaves ? in.pc16 : in.pc4;
+    const size_t launch_pc = a.static_lds + lds_bytes_pc(in.features, p.pc_waves, in.stack_depth, p.n_lds_nodes_pc,
+                                                          p.lds_items_pc, p.lds_spheres_pc);
+    LDS_REQUIRE(launch_pc <= kLdsPerCu / (p.pc_grid / in.cus));
+    LDS_REQUIRE(p.pc_grid / in.cus * p.pc_waves <= 4 * waves_per_simd(a.num_regs) || p.pc_grid == in.cus);
+    if (p.lds_items_pc || p.lds_spheres_pc)
+      LDS_REQUIRE(p.n_lds_nodes_pc == in.n_nodes && p.lds_items_pc == in.n_items && p.lds_spheres_pc == in.n_spheres);
+  }
+  LDS_REQUIRE(p.lds_perlin == 0 || (p.lds_perlin == 1 && (in.features & RT_FEAT_NOISE) && in.n_perlin == 1));
+  return true;
+}
+
+int lds_sweep() {
+  const int kRegs[] = {8, 96, 120, 128, 129, 168, 256, 512};
+  const int kStatic[] = {0, 6144, 24576, 65536};
+  const int kDepths[] = {1, 13, 21, RT_STACK_DEPTH, 46, RT_STACK_DEPTH4};
+  const int kNodes[] = {0, 485, 2000, 100000};
+  const int kPrims[][2] = {{0, 0}, {486, 486}, {486, 0}, {4000, 4000}};
+  long n_plans = 0;
+  std::string why;
+  for (int regs : kRegs)
+    for (int slds : kStatic)
+      for (int depth : kDepths)
+        for (int nodes : kNodes)
+          for (const auto &prims : kPrims)
+            for (int features = 0; features < 64; ++features)
+              for (int cus : {1, 256})
+                for (const Tune &tu : kLdsTunes) {
+                  LdsPlanInput in{};
+                  in.render = KernelAttrs{regs, slds};
+                  // the persistent instances: the 16-wave form with four times the one-unit
+                  // block's static LDS, as the real ones
+                  in.pc16 = KernelAttrs{regs, 4 * slds};
+                  in.pc4 = KernelAttrs{regs, slds};
+                  in.cus = cus;
+                  in.features = features;
+                  in.stack_depth = depth;
+                  in.n_nodes = nodes;
+                  in.n_items = prims[0];
+                  in.n_spheres = prims[1];
+                  in.n_perlin = nodes % 3; // 0, 2, 2, 1
+                  const SceneLdsPlan p = plan_scene_lds(in, tu.t);
+                  ++n_plans;
+                  if (!check_lds_plan(in, p, why)) {
+                    std::fprintf(stderr,
+                                 "rtx_plan_check: residency plan: %s\n  %d regs, %d B static, features %d, stack %d, "
+                                 "%d nodes, %d items, %d spheres, %d CUs, tuning %s\n",
+                                 why.c_str(), regs, slds, features, depth, nodes, prims[0], prims[1], cus, tu.name);
+                    return 1;
+                  }
+                }
+  std::printf("rtx_plan_check: %ld residency plans: ok\n", n_plans);
+  return 0;
+}
+
+// The instances' register counts and static LDS in the gfx950 build (`make
+// asm`: build/asm/resource.txt "VGPRs" and "LDS Size [bytes/block]";
+// tools/regs.py prints the former): what hipFuncGetAttributes reports as
+// numRegs and sharedSizeBytes.
+const KernelAttrs kF0{120, 6144}, kF4{150, 6144}, kF5{168, 6144}, kF8{158, 15360}, kF13{168, 15360},
+    kF16{128, 1536}, kF32{128, 6144}, kPc16{128, 24576}, kPc4{128, 6144};
+
+void lds_row(const char *name, KernelAttrs render, int features, int stack_depth, int n_nodes, int n_items,
+             int n_spheres, int n_perlin, const rt_tuning &t, KernelAttrs pc16 = kPc16, KernelAttrs pc4 = kPc4) {
+  LdsPlanInput in{};
+  in.render = render;
+  in.pc16 = pc16;
+  in.pc4 = pc4;
+  in.cus = 256;
+  in.features = features;
+  in.stack_depth = stack_depth;
+  in.n_nodes = n_nodes;
+  in.n_items = n_items;
+  in.n_spheres = n_spheres;
+  in.n_perlin = n_perlin;
+  const SceneLdsPlan p = plan_scene_lds(in, t);
+  const RtkLdsPlan &r = p.render;
+  std::printf("%s: %s; block %d waves/SIMD, %d of %d B, room for %d nodes, %d waves/CU", name,
+              p.outcome == LDS_OK ? "ok" : p.outcome == LDS_STACKS_OVER_SHARE ? "stacks over share" : "unsupported",
+              r.waves_per_simd, r.fixed_bytes, r.block_budget, r.n_nodes, r.resident_waves_per_cu);
+  if (p.outcome != LDS_UNSUPPORTED)
+    std::printf("; %d nodes, %d slots; persistent %d waves x %d: %d nodes, %d items, %d spheres; perlin %d",
+                p.n_lds_nodes, p.wave_slots, p.pc_waves, p.pc_grid, p.n_lds_nodes_pc, p.lds_items_pc,
+                p.lds_spheres_pc, p.lds_perlin);
+  std::printf("\n");
+}
+
+int lds_table() {
+  const rt_tuning def = kLdsTunes[0].t;
+  // C3's shape: everything staged, DESIGN.md §2's byte split (stacks 53,248 +
+  // sums 24,576 + nodes 38,800 + items 15,552 + spheres 31,104 of 163,840 B)
+  lds_row("C3 485 nodes 486 items 486 spheres", kF0, 0, 13, 485, 486, 486, 0, def);
+  lds_row("tree over the free bytes: prefix, no prims", kF0, 0, 20, 5000, 5001, 5001, 0, def);
+  lds_row("tree fits, prims do not", kF0, 0, 13, 485, 3000, 3000, 0, def);
+  lds_row("tree and items fit, no spheres", kF0, 0, 13, 485, 486, 0, 0, def);
+  lds_row("empty world", kF0, 0, 1, 0, 0, 0, 0, def);
+  lds_row("4-wide 1000 nodes", kF32, 32, 22, 1000, 4096, 4096, 0, def);
+  lds_row("4-wide depth 34: 16-wave stacks fill the CU", kF32, 32, 34, 1000, 4096, 4096, 0, def);
+  lds_row("4-wide depth 34, 32 KB static at 16 waves: 4-wave blocks", kF32, 32, 34, 1000, 4096, 4096, 0, def,
+          KernelAttrs{128, 32768});
+  lds_row("4-wide depth 37: no shape fits, stacks over share", kF32, 32, 37, 1000, 4096, 4096, 0, def);
+  lds_row("persistent instance at 168 registers: still one 16-wave block per CU", kF0, 0, 13, 485, 486, 486, 0, def,
+          KernelAttrs{168, 24576}, KernelAttrs{168, 6144});
+  lds_row("rich set (media + lights) at 3 waves/SIMD", kF5, 5, 10, 100, 60, 10, 0, def);
+  lds_row("flat world: one-wave blocks", kF16, 16, 1, 0, 8, 8, 0, def);
+  lds_row("lds_cap below the fixed bytes", kF0, 0, 13, 485, 486, 486, 0, kLdsTunes[1].t);
+  lds_row("lds_cap=30000", kF0, 0, 13, 485, 486, 486, 0, kLdsTunes[2].t);
+  lds_row("4-wide depth 46: stacks over share, 3 blocks per CU", kF32, 32, 46, 1000, 4096, 4096, 0, def);
+  lds_row("fixed bytes above 64 KB", kF32, 32, 64, 1000, 4096, 4096, 0, def);
+  lds_row("lds_nodes=100", kF0, 0, 13, 485, 486, 486, 0, kLdsTunes[4].t);
+  lds_row("lds_nodes=-1", kF0, 0, 13, 485, 486, 486, 0, kLdsTunes[5].t);
+  lds_row("lds_cap=4096 lds_nodes=100 pc_waves=4", kF0, 0, 13, 485, 486, 486, 0, kLdsTunes[11].t);
+  lds_row("lds_nodes_pc=100", kF0, 0, 13, 485, 486, 486, 0, kLdsTunes[6].t);
+  lds_row("lds_nodes_pc=-1", kF0, 0, 13, 485, 486, 486, 0, kLdsTunes[7].t);
+  lds_row("no_lds_prims", kF0, 0, 13, 485, 486, 486, 0, kLdsTunes[8].t);
+  lds_row("pc_waves=4", kF0, 0, 13, 485, 486, 486, 0, kLdsTunes[9].t);
+  lds_row("pc_waves=4 small tree", kF0, 0, 8, 85, 86, 86, 0, kLdsTunes[9].t);
+  lds_row("noise, one Perlin table", kF8, 8, 10, 100, 101, 101, 1, def);
+  lds_row("noise, no_lds_perlin", kF8, 8, 10, 100, 101, 101, 1, kLdsTunes[10].t);
+  lds_row("noise, two Perlin tables", kF8, 8, 10, 100, 101, 101, 2, def);
+  lds_row("one Perlin table, no noise texture", kF0, 0, 10, 100, 101, 101, 1, def);
+  lds_row("C4's set (media, lights, noise)", kF13, 13, 12, 300, 301, 250, 1, def);
+  // rt_tuning.extra_features is OR'ed into the instance key before the plan
+  lds_row("extra_features=4: the lights instance", kF4, 0 | 4, 13, 485, 486, 486, 0, def);
+  const char *const verdicts[] = {"fits", "too deep", "over share"};
+  std::printf("collapse 4 levels: %s\n", verdicts[collapse4_verdict(kF32, 0, 4, 0)]);
+  std::printf("collapse 11 levels (stack 34): %s\n", verdicts[collapse4_verdict(kF32, 0, 11, 0)]);
+  std::printf("collapse 12 levels (stack 37): %s\n", verdicts[collapse4_verdict(kF32, 0, 12, 0)]);
+  std::printf("collapse 21 levels (stack 64): %s\n", verdicts[collapse4_verdict(kF32, 0, 21, 0)]);
+  std::printf("collapse 22 levels (stack 67): %s\n", verdicts[collapse4_verdict(kF32, 0, 22, 0)]);
+  std::printf("collapse 4 levels, lds_cap=4096: %s\n", verdicts[collapse4_verdict(kF32, 0, 4, 4096)]);
+  return 0;
+}
+
 } // namespace
 
 int main(int argc, char **argv) {
   if (argc == 2 && !std::strcmp(argv[1], "--table")) return table();
+  if (argc == 2 && !std::strcmp(argv[1], "--lds-table")) return lds_table();
   if (argc != 1) {
-    std::fprintf(stderr, "usage: rtx_plan_check [--table]\n");
+    std::fprintf(stderr, "usage: rtx_plan_check [--table | --lds-table]\n");
     return 2;
   }
-  return sweep();
+  const int rc = sweep();
+  return rc ? rc : lds_sweep();
 }

@@ -65,33 +65,19 @@ extern "C" int emu_render(const rt_scene_desc *desc, const rt_frame *f, const rt
   // features bit 5 (F_BVH4): walk the 4-wide collapse of the same tree, as the
   // library does for large scenes (rt_api.cpp)
   const bool bvh4 = (features & F_BVH4) && !H.root_is_leaf && !H.nodes.empty();
-  int depth4 = 0;
-  if (bvh4) depth4 = rtx::collapse_bvh4(H.nodes, H.nodes4);
-  DScene S;
-  S.nodes = bvh4 ? (const DNode *)(const void *)H.nodes4.data() : H.nodes.data();
-  S.items = H.items.data();
-  S.bitems = H.bitems.data();
-  S.mitems = H.mitems.data();
-  S.mbox = H.mbox.data();
-  S.n_mitems = (int32_t)H.mitems.size();
-  S.xforms = H.xforms.data();
-  S.spheres = H.spheres.data();
-  S.quads = H.quads.data();
-  S.media = H.media.data();
-  S.mats = H.mats.data();
-  S.texs = H.texs.data();
-  S.perlin = H.perlin.data();
-  S.lights = H.lights.data();
-  S.n_lights = (int32_t)H.lights.size();
-  S.n_nodes = (int32_t)(bvh4 ? H.nodes4.size() : H.nodes.size());
-  S.root_is_leaf = H.root_is_leaf;
-  S.n_root_items = H.n_root_items;
+  if (bvh4) {
+    H.bvh_depth4 = rtx::collapse_bvh4(H.nodes, H.nodes4);
+    H.bvh_arity = 4;
+  }
+  DScene S = rtx::bind_host_scene(H);
+  if (bvh4) {
+    S.nodes = (const DNode *)(const void *)H.nodes4.data();
+    S.n_nodes = (int32_t)H.nodes4.size();
+  }
   S.features = features;
-  S.static_spheres = rtx::all_spheres_static(H);
-  // rt_scene_create's rule: the walk pushes with no overflow check, so a tree
-  // deeper than the stack is refused, not clamped
-  S.stack_depth = bvh4 ? rtx::bvh4_stack_depth(depth4) : std::max(1, H.bvh_depth + 1);
-  if (S.stack_depth > (bvh4 ? RT_STACK_DEPTH4 : RT_STACK_DEPTH)) return -2;
+  // rt_scene_create's rule: a tree deeper than the stack is refused, not clamped
+  S.stack_depth = rtx::traversal_stack_depth(H, err);
+  if (!S.stack_depth) return -2;
   S.n_lds_nodes = S.n_nodes; // host: the whole tree is the "LDS" copy
   // in the form the kernel stages it: DNode4 as is, binary nodes as DNodeL
   std::vector<DNodeL> lnodes_l;
