@@ -41,6 +41,10 @@
  *                        (DynamicCamera.cpp:96-200); these stop sampling the 8x8 tiles whose
  *                        estimate has converged (launches over a tile list, per-pixel moments,
  *                        per-tile error, a display scale per tile)
+ *   rt_render_guides_device / rt_denoise_workspace_bytes / rt_denoise_device
+ *                     <- no counterpart: DynamicCamera displays the raw accumulation
+ *                        (DynamicCamera.cpp:284-300); these give the display first-hit
+ *                        albedo / normal / depth sums and an edge-avoiding filter over them
  *   rt_last_error     <- replaces CUDA_CHECK's exit() and the converters' exceptions
  *                        (CudaMemoryUtility.cuh:9-15, HittableConverter.cuh:103-108): errors are
  *                        returned as negative codes, never thrown or exit()ed across the ABI.
@@ -524,6 +528,81 @@ int rt_adaptive_select_device(const double *device_s1, const double *device_s2,
    1 / max(1, tile_strata[tile of the pixel]) per pixel. */
 int rt_to_bytes_tiles_device(const double *device_rgb, const int32_t *device_tile_strata, const rt_frame *frame,
                              uint8_t *device_bytes, void *hip_stream);
+
+/* ---- denoised display (functions added under ABI 5: no struct or signature
+   above changed) ------------------------------------------------------------
+   First-hit guide buffers and an edge-avoiding a-trous filter for the first
+   frames after a camera move (rtx/denoise.py drives these and states the
+   filter in NumPy; DESIGN.md "Denoised display"). */
+
+/* Per-pixel guide sums: albedo r,g,b; normal x,y,z; depth; hits. */
+#define RT_GUIDE_CHANNELS 8
+
+/* Adds (accumulate 1) or writes (0) the first-hit guide sums of strata
+   [sample_begin, +sample_count) of rows [row_begin, row_end) into
+   device_guides ([rows][W][RT_GUIDE_CHANNELS] doubles), asynchronously on
+   hip_stream.  A sample's ray is the render's own camera ray of that stratum
+   (same seed, jitter, defocus, time); its first hit is the render's primary
+   segment's, constant media included.  Per sample: a miss adds albedo (1,1,1)
+   and nothing else; a hit adds hits 1, depth t * |d|, the surface normal
+   (0 for a medium) and the albedo -- the texture value (lambertian, a
+   medium's isotropic phase), the metal's albedo, or (1,1,1) (dielectric,
+   diffuse light).  One wavefront per 8x8 tile, one lane per pixel, strata
+   added in ascending order: the result is bit-reproducible, and strata [0,4)
+   in one call equal [0,2) then [2,4) accumulated bit for bit.  Pixels outside
+   the image are not written.  params->output must be RT_OUT_SUM; tile_first /
+   tile_stride / layout / strata_chunks must be 0 / 0-or-1 / RT_LAYOUT_FRAME /
+   0; anything else is RT_ERR_INVALID before anything is queued.  The launch
+   joins the scene's launch chain like rt_render_device (rt_scene_destroy waits
+   for it). */
+int rt_render_guides_device(rt_scene *scene, const rt_frame *frame, const rt_render_params *params,
+                            double *device_guides, void *hip_stream);
+
+/* The filter's defaults: chosen by the sweep of tools/denoise_bench.py
+   (DESIGN.md "Denoised display" records it). */
+#define RT_DENOISE_PASSES 5
+#define RT_DENOISE_SIGMA_NORMAL 0.2
+#define RT_DENOISE_SIGMA_DEPTH 0.01
+#define RT_DENOISE_SIGMA_HIT 0.1
+#define RT_DENOISE_SIGMA_COLOR 64.0
+#define RT_DENOISE_MAX_PASSES 8
+
+typedef struct rt_denoise_params {
+  int32_t passes;      /* a-trous passes, step 2^k in pass k; 0: RT_DENOISE_PASSES; < 0: none
+                          (prepare + remodulate only); > RT_DENOISE_MAX_PASSES: RT_ERR_INVALID */
+  int32_t reserved;
+  double sigma_normal; /* 0: default; < 0: term off */
+  double sigma_depth;  /* 0: default; < 0: term off */
+  double sigma_hit;    /* 0: default; < 0: term off */
+  double sigma_color;  /* 0: default; < 0: term off; halves every pass */
+} rt_denoise_params;
+
+/* Bytes of workspace rt_denoise_device needs for this frame (a multiple of
+   256): four fp32 float4 planes, 64 B per pixel. */
+int rt_denoise_workspace_bytes(const rt_frame *frame, int64_t *bytes);
+
+/* out = the a-trous-filtered, scaled radiance of device_rgb, steered by the
+   guides.  Per pixel: c = rgb * scale (rgb_scale, or with device_tile_strata
+   1 / max(1, strata of the pixel's 8x8 tile) as rt_to_bytes_tiles_device);
+   a = albedo / g, a_d = max(a, 0.01) per channel, e = c / a_d (the filtered
+   signal); n = normal / g (not renormalised), h = hits / g,
+   z = depth / max(hits, 1), all rounded to fp32.  Pass k = 0 .. passes - 1,
+   step s = 2^k: taps q = p + s (di, dj), di, dj in -2..2, B3-spline weights
+   b = (1/16, 1/4, 3/8, 1/4, 1/16), taps outside the image skipped; the centre
+   weighs b2 b2; every other tap b_di b_dj exp(-min(x, 80)) with x the sum of
+   the enabled terms |n_p - n_q|^2 / sn^2, |z_p - z_q| / (sz max(z_p, z_q,
+   1e-30) s max(|di|, |dj|)), (h_p - h_q)^2 / sh^2 and |e_p - e_q|^2 /
+   ((sc 2^-k)^2 (y_p^2 + 1e-4)), y the Rec. 709 luminance of e; a tap whose e
+   is not finite weighs 0 (a non-finite e_p has no colour term);
+   e'_p = sum w e_q / sum w, or e_p itself when sum w = 0.  out = e a_d.
+   device_rgb and the guides are only read; device_out may be device_rgb and
+   must not overlap the workspace (256-B aligned, caller-owned: the library
+   allocates nothing and keeps no state).  Needs no rt_scene; runs on the
+   current device. */
+int rt_denoise_device(const rt_frame *frame, const double *device_rgb, double rgb_scale,
+                      const int32_t *device_tile_strata, const double *device_guides, int32_t guide_strata,
+                      const rt_denoise_params *params, void *device_workspace, double *device_out,
+                      void *hip_stream);
 
 /* ---- tile exchange (multi-GPU tile sharding) ------------------------------ */
 /* Tile-layout chunk partials [tile][chunk][64][3] (rt_render_device with

@@ -936,6 +936,77 @@ int rt_to_bytes_tiles_device(const double *device_rgb, const int32_t *device_til
   return RT_OK;
 }
 
+// ---------------------------------------------------------------- denoised display
+// The guide launch: launch_geometry's row / stratum / seed fields, one
+// wavefront per tile of the row range, nothing of the render's plan (no
+// units, no order slot, no scratch).  It joins the scene's chain only so that
+// destroy waits for it: the kernel reads the scene tables.
+int rt_render_guides_device(rt_scene *s, const rt_frame *f, const rt_render_params *p, double *dev_guides,
+                            void *hip_stream) {
+  if (!s || !dev_guides || !p || !f) return set_err(RT_ERR_INVALID, "null argument");
+  if (p->output != RT_OUT_SUM) return set_err(RT_ERR_INVALID, "guides are raw sums: output must be RT_OUT_SUM");
+  if (p->tile_first != 0 || (p->tile_stride != 0 && p->tile_stride != 1) || p->layout != RT_LAYOUT_FRAME ||
+      p->strata_chunks != 0)
+    return set_err(RT_ERR_INVALID, "a guide launch takes tile_first 0, tile_stride 0 or 1, "
+                                   "RT_LAYOUT_FRAME, strata_chunks 0");
+  DCamera C;
+  DLaunch L;
+  int rc = to_device_camera(f, C);
+  if (rc) return rc;
+  if ((rc = to_launch(f, p, L))) return rc;
+  DeviceGuard g(s->device);
+  hipStream_t st = (hipStream_t)hip_stream;
+  if ((rc = order_after_last(s, st))) return rc;
+  hipError_t e = rtk_launch_guides(&s->ds, &C, &L, dev_guides, st);
+  if (e != hipSuccess) return hip_err(e, "guide kernel launch");
+  return mark_last(s, st);
+}
+
+int rt_denoise_workspace_bytes(const rt_frame *f, int64_t *bytes) {
+  int64_t tiles = 0;
+  if (int rc = frame_tiles(f, tiles)) return rc;
+  if (!bytes) return set_err(RT_ERR_INVALID, "null argument");
+  *bytes = (int64_t)rtk_denoise_workspace_bytes(f->image_width, f->image_height);
+  return RT_OK;
+}
+
+int rt_denoise_device(const rt_frame *f, const double *device_rgb, double rgb_scale,
+                      const int32_t *device_tile_strata, const double *device_guides, int32_t guide_strata,
+                      const rt_denoise_params *params, void *device_workspace, double *device_out,
+                      void *hip_stream) {
+  int64_t tiles = 0;
+  if (int rc = frame_tiles(f, tiles)) return rc;
+  if (!device_rgb || !device_guides || !device_workspace || !device_out)
+    return set_err(RT_ERR_INVALID, "null argument");
+  if (guide_strata < 1) return set_err(RT_ERR_INVALID, "guide_strata must be >= 1");
+  if (((uintptr_t)device_workspace & 255) != 0) return set_err(RT_ERR_INVALID, "workspace must be 256-B aligned");
+  {
+    const uintptr_t w0 = (uintptr_t)device_workspace;
+    const uintptr_t w1 = w0 + rtk_denoise_workspace_bytes(f->image_width, f->image_height);
+    const uintptr_t o0 = (uintptr_t)device_out;
+    const uintptr_t o1 = o0 + (size_t)f->image_width * f->image_height * 3 * sizeof(double);
+    if (o0 < w1 && w0 < o1) return set_err(RT_ERR_INVALID, "device_out overlaps the workspace");
+  }
+  rt_denoise_params q{};
+  if (params) q = *params;
+  if (q.passes > RT_DENOISE_MAX_PASSES)
+    return set_err(RT_ERR_INVALID, "passes must be at most " + std::to_string(RT_DENOISE_MAX_PASSES));
+  const double sig[4] = {q.sigma_normal, q.sigma_depth, q.sigma_hit, q.sigma_color};
+  for (double v : sig)
+    if (v != v) return set_err(RT_ERR_INVALID, "a sigma is NaN");
+  auto pick = [](double v, double dflt) { return v == 0.0 ? dflt : v; }; // < 0: off
+  const int passes = q.passes == 0 ? RT_DENOISE_PASSES : q.passes;
+  hipError_t e = rtk_launch_denoise(f->image_width, f->image_height, device_rgb, rgb_scale, device_tile_strata,
+                                    device_guides, guide_strata, passes,
+                                    pick(q.sigma_normal, RT_DENOISE_SIGMA_NORMAL),
+                                    pick(q.sigma_depth, RT_DENOISE_SIGMA_DEPTH),
+                                    pick(q.sigma_hit, RT_DENOISE_SIGMA_HIT),
+                                    pick(q.sigma_color, RT_DENOISE_SIGMA_COLOR), device_workspace, device_out,
+                                    (hipStream_t)hip_stream);
+  if (e != hipSuccess) return hip_err(e, "denoise launch");
+  return RT_OK;
+}
+
 int rt_render_stats(rt_scene *s, const rt_frame *f, const rt_render_params *p,
                     rt_path_stats *stats) {
   if (!s || !stats || !p) return set_err(RT_ERR_INVALID, "null argument");

@@ -1,6 +1,6 @@
 // rt_kernels.h — every rtk_* launcher, declared once: included by the files
-// that define them (rt_kernel.hip, rt_frame.hip, rt_adaptive.hip,
-// rt_bvh_build.hip, rt_bvh_sah.hip) and by their caller (rt_api.cpp), so a
+// that define them (rt_kernel.hip, rt_frame.hip, rt_adaptive.hip, rt_guides.hip,
+// rt_denoise.hip, rt_bvh_build.hip, rt_bvh_sah.hip) and by their caller (rt_api.cpp), so a
 // definition whose parameter list drifts from its callers' no longer compiles.
 #ifndef RT_KERNELS_H
 #define RT_KERNELS_H
@@ -48,6 +48,17 @@ hipError_t rtk_launch_adaptive_select(const double *s1, const double *s2, const 
                                       int32_t *count_out, double *tile_error, hipStream_t stream);
 hipError_t rtk_launch_to_bytes_tiles(const double *rgb, const int32_t *tile_strata, int W, int H, uint8_t *bytes,
                                      hipStream_t stream);
+
+// ---- rt_guides.hip: first-hit guide sums [rows][W][8] (P: launch_geometry's fields; no plan)
+hipError_t rtk_launch_guides(const DScene *S, const DCamera *C, const DLaunch *P, double *out,
+                             hipStream_t stream);
+
+// ---- rt_denoise.hip: the a-trous filter (sigmas resolved: > 0 on, <= 0 off; passes < 0: none)
+size_t rtk_denoise_workspace_bytes(int W, int H);
+hipError_t rtk_launch_denoise(int W, int H, const double *rgb, double scale, const int32_t *tile_strata,
+                              const double *guides, int guide_strata, int passes, double sigma_n,
+                              double sigma_z, double sigma_h, double sigma_c, void *workspace, double *out,
+                              hipStream_t stream);
 
 // ---- rt_bvh_build.hip, rt_bvh_sah.hip: the device BVH builders
 size_t rtk_lbvh_temp_bytes(int n);

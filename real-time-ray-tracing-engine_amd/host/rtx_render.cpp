@@ -9,6 +9,7 @@
 //              [--width N] [--samples N] [--depth N]
 //              [--scene file.json] [--seed S] [--device D] [--gpus N] [--shards K]
 //              [--backend hip|cpu] [--threads N] [--dump-desc]
+//              [--denoise [--denoise-passes N]]
 //
 // Mapping of the reference flags onto this library:
 //   --camera static   the only mode; "dynamic" is the SDL window (out of scope,
@@ -43,9 +44,18 @@
 // rt_multi_render); --shards K (default N) splits
 // the frame into K tile shards, K > N putting several shards on one device.
 // The sharded frame is bit-identical to the one-device frame (rt_api.h).
+// --denoise (HIP backend, one device) filters the finished frame on the device
+// before it is quantised: first-hit guides over every stratum of the render
+// (rt_render_guides_device), the a-trous filter with the library's defaults
+// (rt_denoise_device; --denoise-passes N overrides the pass count), and the
+// PPM is rt_to_bytes_device of the filtered frame.  Without the flag the bytes
+// are what they were.  With --backend cpu, or --gpus / --shards above 1, the
+// flag is refused with a message.
 #include "rt_api.h"
 #include "rt_cpu.h"
 #include "scene_json.hpp"
+
+#include <hip/hip_runtime_api.h> // --denoise: the frame's device buffers
 
 #include <chrono>
 #include <cmath>
@@ -70,6 +80,8 @@ struct Options {
   int gpus = 1, shards = 0;
   bool cpu = false; // --backend cpu
   int threads = 0;  // --threads (CPU backend); 0: rt_cpu_default_threads()
+  bool denoise = false;   // --denoise
+  int denoise_passes = 0; // --denoise-passes; 0: the library's default
 };
 
 bool parse_int(const char *s, int &out) {
@@ -128,7 +140,7 @@ Options parse(int argc, char **argv) {
         }
       }
     } else if (a == "--width" || a == "--samples" || a == "--depth" || a == "--device" ||
-               a == "--gpus" || a == "--shards" || a == "--threads") {
+               a == "--gpus" || a == "--shards" || a == "--threads" || a == "--denoise-passes") {
       if (const char *v = need("a number")) {
         int x;
         if (!parse_int(v, x)) {
@@ -149,6 +161,8 @@ Options parse(int argc, char **argv) {
           o.shards = x;
         } else if (a == "--threads") {
           o.threads = x;
+        } else if (a == "--denoise-passes") {
+          o.denoise_passes = x;
         } else {
           o.device = x;
         }
@@ -159,6 +173,8 @@ Options parse(int argc, char **argv) {
       if (const char *v = need("a number")) o.seed = std::strtoull(v, nullptr, 0);
     } else if (a == "--dump-desc") {
       o.dump_desc = true;
+    } else if (a == "--denoise") {
+      o.denoise = true;
     } else {
       o.any_errors = true;
       std::cerr << "Unknown option: " << a << std::endl;
@@ -175,6 +191,18 @@ Options parse(int argc, char **argv) {
   if (o.cpu && (o.gpus > 1 || o.shards > 1)) {
     o.any_errors = true;
     std::cerr << "--gpus / --shards are GPU options; --backend cpu uses --threads\n";
+  }
+  if (o.denoise && o.cpu) {
+    o.any_errors = true;
+    std::cerr << "--denoise runs on the GPU library; it is not provided with --backend cpu\n";
+  }
+  if (o.denoise && (o.gpus > 1 || o.shards > 1)) {
+    o.any_errors = true;
+    std::cerr << "--denoise filters on one device; it is not provided with --gpus / --shards above 1\n";
+  }
+  if (o.denoise_passes > RT_DENOISE_MAX_PASSES) {
+    o.any_errors = true;
+    std::cerr << "--denoise-passes must be at most " << RT_DENOISE_MAX_PASSES << "\n";
   }
   if (!o.use_static && output_selected)
     std::cerr << "You can only set an output file if the static camera is selected, ignoring...\n";
@@ -203,7 +231,9 @@ void print_help() {
          "  --shards <int>             Tile shards over those devices (default: --gpus)\n"
          "  --backend <hip|cpu>        GPU library (default) or the CPU backend\n"
          "  --threads <int>            CPU backend threads (default: the CPUs this process may use)\n"
-         "  --dump-desc                Print the flattened scene description and exit\n";
+         "  --dump-desc                Print the flattened scene description and exit\n"
+         "  --denoise                  Filter the frame on the GPU (first-hit guides + a-trous) before writing\n"
+         "  --denoise-passes <int>     A-trous passes (default: the library's; < 0: none)\n";
 }
 
 std::string exe_dir(const char *argv0) {
@@ -316,6 +346,58 @@ unsigned char to_byte(double x) {
 int fail_rt(const char *what) {
   std::cerr << "[ERROR] " << what << ": " << rt_last_error() << "\n";
   return 1;
+}
+
+// --denoise: the frame's sample sums (host) -> write_color bytes of the
+// filtered frame.  Guides over all n_strata strata of the render, the filter
+// in place on the uploaded frame, rt_to_bytes_device with scale 1; everything
+// on the null stream of the scene's device.  Returns 0, or 1 after printing.
+int denoise_bytes(rt_scene *scene, const rt_frame &frame, int device, unsigned long long seed, int n_strata,
+                  int passes, const std::vector<double> &sum, std::vector<unsigned char> &bytes) {
+  const size_t px = (size_t)frame.image_width * frame.image_height;
+  int64_t ws_bytes = 0;
+  if (rt_denoise_workspace_bytes(&frame, &ws_bytes) != RT_OK) return fail_rt("denoise workspace");
+  double *d_rgb = nullptr, *d_guides = nullptr;
+  void *d_ws = nullptr;
+  unsigned char *d_bytes = nullptr;
+  auto free_all = [&]() {
+    (void)hipFree(d_rgb);
+    (void)hipFree(d_guides);
+    (void)hipFree(d_ws);
+    (void)hipFree(d_bytes);
+  };
+  auto hip_fail = [&](hipError_t e, const char *what) {
+    std::cerr << "[ERROR] " << what << ": " << hipGetErrorString(e) << "\n";
+    free_all();
+    return 1;
+  };
+  hipError_t e = hipSetDevice(device);
+  if (e == hipSuccess) e = hipMalloc((void **)&d_rgb, px * 3 * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc((void **)&d_guides, px * RT_GUIDE_CHANNELS * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc(&d_ws, (size_t)ws_bytes);
+  if (e == hipSuccess) e = hipMalloc((void **)&d_bytes, px * 3);
+  if (e == hipSuccess) e = hipMemcpy(d_rgb, sum.data(), px * 3 * sizeof(double), hipMemcpyHostToDevice);
+  if (e != hipSuccess) return hip_fail(e, "denoise buffers");
+  rt_render_params p{};
+  p.sample_begin = 0;
+  p.sample_count = n_strata;
+  p.seed = seed;
+  p.output = RT_OUT_SUM;
+  rt_denoise_params dp{};
+  dp.passes = passes;
+  if (rt_render_guides_device(scene, &frame, &p, d_guides, nullptr) != RT_OK ||
+      rt_denoise_device(&frame, d_rgb, frame.pixel_samples_scale, nullptr, d_guides, n_strata, &dp, d_ws, d_rgb,
+                        nullptr) != RT_OK ||
+      rt_to_bytes_device(d_rgb, (int64_t)px, 1.0, d_bytes, nullptr) != RT_OK) {
+    int rc = fail_rt("denoise");
+    free_all();
+    return rc;
+  }
+  bytes.resize(px * 3);
+  e = hipMemcpy(bytes.data(), d_bytes, px * 3, hipMemcpyDeviceToHost); // waits for the null stream
+  if (e != hipSuccess) return hip_fail(e, "denoise copy");
+  free_all();
+  return 0;
 }
 
 } // namespace
@@ -439,6 +521,11 @@ int main(int argc, char **argv) {
     std::clog << "\rStrata remaining: " << (n_strata - s - cnt) << ' ' << std::flush;
   }
   double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  std::vector<unsigned char> filtered; // --denoise: the PPM's bytes
+  if (opt.denoise && denoise_bytes(scene, frame, opt.device, opt.seed, n_strata, opt.denoise_passes, sum, filtered)) {
+    release();
+    return 1;
+  }
   release();
   std::clog << "\rDone. " << W << "x" << H << " @ " << n_strata << " spp, "
             << (double)W * H * n_strata / secs / 1e6 << " Msamples/s";
@@ -460,8 +547,10 @@ int main(int argc, char **argv) {
   const double scale = frame.pixel_samples_scale;
   char line[32];
   for (size_t px = 0; px < (size_t)W * H; ++px) {
-    int n = std::snprintf(line, sizeof line, "%d %d %d\n", to_byte(scale * sum[3 * px]),
-                          to_byte(scale * sum[3 * px + 1]), to_byte(scale * sum[3 * px + 2]));
+    int n = opt.denoise ? std::snprintf(line, sizeof line, "%d %d %d\n", filtered[3 * px], filtered[3 * px + 1],
+                                        filtered[3 * px + 2])
+                        : std::snprintf(line, sizeof line, "%d %d %d\n", to_byte(scale * sum[3 * px]),
+                                        to_byte(scale * sum[3 * px + 1]), to_byte(scale * sum[3 * px + 2]));
     buf.append(line, (size_t)n);
   }
   std::fwrite(buf.data(), 1, buf.size(), f);

@@ -97,6 +97,7 @@ class RenderParams(C.Structure):
 
 
 RT_LAYOUT_FRAME, RT_LAYOUT_TILES = 0, 1
+RT_GUIDE_CHANNELS = 8  # rt_render_guides_device: albedo r,g,b; normal x,y,z; depth; hits
 RT_CHUNKS_AUTO = -1  # strata_chunks: the library's units for a tile subset, per-tile sums out
 
 
@@ -144,6 +145,33 @@ class Tuning(C.Structure):
                 ("probe_strata", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
+class DenoiseParams(C.Structure):
+    """rt_denoise_params: zero-filled = every default (include/rt_api.h
+    RT_DENOISE_*); a negative sigma switches its term off, passes < 0 the filter."""
+    _fields_ = [("passes", C.c_int32), ("reserved", C.c_int32),
+                ("sigma_normal", C.c_double), ("sigma_depth", C.c_double),
+                ("sigma_hit", C.c_double), ("sigma_color", C.c_double)]
+
+
+# include/rt_api.h RT_DENOISE_*: the shipped defaults (tests/test_denoise.py reads
+# the header's values and compares)
+RT_DENOISE_PASSES, RT_DENOISE_MAX_PASSES = 5, 8
+RT_DENOISE_SIGMA_NORMAL, RT_DENOISE_SIGMA_DEPTH = 0.2, 0.01
+RT_DENOISE_SIGMA_HIT, RT_DENOISE_SIGMA_COLOR = 0.1, 64.0
+
+
+def denoise_params(p=None):
+    """A DenoiseParams from None (the defaults), a DenoiseParams, or a dict of its fields."""
+    if p is None or isinstance(p, DenoiseParams):
+        return p
+    out = DenoiseParams()
+    for k, v in dict(p).items():
+        if k not in dict(DenoiseParams._fields_):
+            raise KeyError("unknown rt_denoise_params field %r" % k)
+        setattr(out, k, v)
+    return out
+
+
 def tuning(t=None):
     """A Tuning from None (the default), a Tuning, or a dict of its fields."""
     if t is None or isinstance(t, Tuning):
@@ -166,4 +194,5 @@ EXPORTS = (
     "rt_scene_create_tuned", "rt_multi_create_tuned",
     "rt_render_tiles_device", "rt_adaptive_update_device", "rt_adaptive_select_device",
     "rt_to_bytes_tiles_device",
+    "rt_render_guides_device", "rt_denoise_workspace_bytes", "rt_denoise_device",
 )

@@ -336,4 +336,5 @@ def for_renderer(renderer, frame, seed=0, threshold=0.0, floor=1e-3, min_batches
     ar = AdaptiveRenderer(render_tiles_fn, HipOps(dev, st), frame, seed, threshold, floor, min_batches,
                           batch_strata, check_every)
     ar.stream = st
+    ar.renderer = renderer  # rtx.denoise.DenoisedDisplay launches its guides on it
     return ar

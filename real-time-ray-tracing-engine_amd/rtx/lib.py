@@ -70,6 +70,11 @@ def load():
                                             C.c_double, C.c_double, C.c_int32, C.c_void_p, C.c_int32,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.rt_to_bytes_tiles_device.argtypes = [C.c_void_p, C.c_void_p, P(abi.Frame), C.c_void_p, C.c_void_p]
+    L.rt_render_guides_device.argtypes = [C.c_void_p, P(abi.Frame), P(abi.RenderParams), C.c_void_p,
+                                          C.c_void_p]
+    L.rt_denoise_workspace_bytes.argtypes = [P(abi.Frame), P(C.c_int64)]
+    L.rt_denoise_device.argtypes = [P(abi.Frame), C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_int32,
+                                    P(abi.DenoiseParams), C.c_void_p, C.c_void_p, C.c_void_p]
     for name in abi.EXPORTS:
         getattr(L, name).restype = C.c_char_p if name == "rt_last_error" else C.c_int
     if L.rt_abi_version() != abi.RT_ABI_VERSION:

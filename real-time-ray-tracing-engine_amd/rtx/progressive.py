@@ -125,6 +125,7 @@ def for_renderer(renderer, frame, seed=0, device=None, stream=None):
 
     pr = ProgressiveRenderer(render_fn, frame, acc, seed)
     pr.stream = st
+    pr.renderer = renderer  # rtx.denoise.DenoisedDisplay launches its guides on it
     return pr
 
 
@@ -176,9 +177,13 @@ class DisplayPipeline:
             img = pipe.present()         # bytes of frame k-1 (None at first)
     """
 
-    def __init__(self, pr, depth=2):
+    def __init__(self, pr, depth=2, bytes_fn=None):
         import torch
         self.pr = pr
+        # bytes_fn(pr, out): the frame's bytes into `out` on the render stream
+        # (default: the raw accumulation's; rtx.denoise.DenoisedDisplay.bytes_into
+        # delivers the filtered frame's)
+        self.bytes_fn = bytes_fn if bytes_fn is not None else frame_bytes
         dev = pr.acc.device
         self.stream = getattr(pr, "stream", None) or torch.cuda.current_stream(dev)
         # one copy stream: the copy split over 2 / 4 streams measured 2x / 4x
@@ -207,7 +212,7 @@ class DisplayPipeline:
             self.copied[b].synchronize()             # the viewer's copy of this slot is free
         self.synced[b] = False
         traced = self.pr.step(n)
-        frame_bytes(self.pr, self.dbytes[b])
+        self.bytes_fn(self.pr, self.dbytes[b])
         self.ready[b].record(self.stream)
         self.copy_stream.wait_event(self.ready[b])
         # the D2H copy on the copy stream: one runtime call (torch's copy_

@@ -130,6 +130,16 @@ class Renderer:
                                               C.c_void_p(tiles_ptr), int(n_tiles),
                                               C.c_void_p(dev_ptr), C.c_void_p(stream_ptr or 0)))
 
+    def render_guides_device(self, frame, dev_ptr, stream_ptr=None, seed=0, rows=(0, 0), samples=(0, -1),
+                             accumulate=1):
+        """First-hit guide sums of those strata (rt_render_guides_device) into
+        the device buffer [rows, W, abi.RT_GUIDE_CHANNELS] float64 at `dev_ptr`:
+        albedo r,g,b; normal x,y,z; depth; hits -- added (accumulate 1) or
+        written (0), asynchronously on `stream_ptr`."""
+        p = self.params(seed, rows, samples, abi.RT_OUT_SUM, accumulate, chunks=0)
+        check(self.lib.rt_render_guides_device(self.handle, C.byref(frame), C.byref(p),
+                                               C.c_void_p(dev_ptr), C.c_void_p(stream_ptr or 0)))
+
     def stats(self, frame, seed=0, rows=(0, 0), samples=(0, -1), tiles=(0, 1),
               layout=abi.RT_LAYOUT_FRAME, chunks=1):
         s = abi.PathStats()
