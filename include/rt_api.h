@@ -45,6 +45,10 @@
  *                     <- no counterpart: DynamicCamera displays the raw accumulation
  *                        (DynamicCamera.cpp:284-300); these give the display first-hit
  *                        albedo / normal / depth sums and an edge-avoiding filter over them
+ *   rt_history_bytes / rt_temporal_device
+ *                     <- no counterpart: DynamicCamera clears its accumulation when the camera
+ *                        moves (DynamicCamera.cpp:269-276); these reproject the previous pose's
+ *                        displayed image into the new pose and blend it with the new samples
  *   rt_last_error     <- replaces CUDA_CHECK's exit() and the converters' exceptions
  *                        (CudaMemoryUtility.cuh:9-15, HittableConverter.cuh:103-108): errors are
  *                        returned as negative codes, never thrown or exit()ed across the ABI.
@@ -603,6 +607,100 @@ int rt_denoise_device(const rt_frame *frame, const double *device_rgb, double rg
                       const int32_t *device_tile_strata, const double *device_guides, int32_t guide_strata,
                       const rt_denoise_params *params, void *device_workspace, double *device_out,
                       void *hip_stream);
+
+/* ---- temporal reprojection (functions added under ABI 5: no struct or
+   signature above changed) --------------------------------------------------
+   Carries the displayed image of the previous camera pose into the new pose
+   wherever the same first-hit surface is still visible, and blends it with the
+   new pose's samples, so that a camera move does not throw the converged frame
+   away (rtx/temporal.py drives this and states it in NumPy; DESIGN.md
+   "Temporal reprojection"). */
+
+/* The reprojection's defaults: the best point of the sweep of
+   tools/temporal_bench.py (DESIGN.md "Temporal reprojection" records it, and
+   what that sweep cannot see: its camera move is small, so it barely prices
+   ghosting at disocclusions.  A host whose camera moves further per frame
+   should pass the sweep's starting point: max_history 32, sigma_depth 0.02,
+   sigma_normal 0.35). */
+#define RT_TEMPORAL_MAX_HISTORY 64
+#define RT_TEMPORAL_SIGMA_DEPTH 0.5
+#define RT_TEMPORAL_SIGMA_NORMAL (-1.0) /* off: the sweep's small camera move never paid for it */
+#define RT_TEMPORAL_HIT_MIN 0.75
+
+typedef struct rt_temporal_params {
+  int32_t max_history; /* cap of the history's sample count n_h; 0: RT_TEMPORAL_MAX_HISTORY;
+                          < 0: RT_ERR_INVALID */
+  int32_t reserved;
+  double sigma_depth;  /* surface test, relative to the distance from the previous camera;
+                          0: default; < 0: test off */
+  double sigma_normal; /* normal test |n_p - n'_q| <= sigma_normal; 0: default; < 0: test off */
+  double hit_min;      /* least hit fraction h of a pixel that takes or leaves history;
+                          0: default; < 0: every pixel */
+} rt_temporal_params;
+
+/* Bytes of one history for this frame (a multiple of 256): two fp32 float4
+   planes, each padded to 256 B, col = (e.r, e.g, e.b, count) first and
+   geo = (n.x, n.y, n.z, z) after it.  A history belongs to the rt_frame it
+   was written at. */
+int rt_history_bytes(const rt_frame *frame, int64_t *bytes);
+
+/* device_out = the new pose's scaled radiance blended with the previous pose's
+   history; device_history_out = the history of this frame.  Per pixel p =
+   (i, j), with rt_denoise_device's quantities c = rgb * scale (rgb_scale, or
+   with device_tile_strata 1 / max(1, strata of the pixel's 8x8 tile)),
+   a_d = max(albedo / g, 0.01), e = c / a_d, n = normal / g, h = hits / g,
+   z = depth / max(hits, 1), and the current count n_c = strata_now, or with
+   device_tile_strata the tile's strata:
+     position    d = pixel00_loc + i pixel_delta_u + j pixel_delta_v - center,
+                 P = center + z d / |d|: the pixel-centre ray; with defocus or
+                 jitter an approximation of where the samples hit.
+     projection  into frame_prev (c', pixel00', du', dv'): v = P - c',
+                 N' = du' x dv', num = (pixel00' - c') . N', den = v . N';
+                 history is possible only if den num > 0 and h >= hit_min;
+                 q = c' + (num / den) v - pixel00', x = q . du' / du' . du',
+                 y = q . dv' / dv' . dv', r = |v|.
+     taps        the four pixels (floor x + a, floor y + b), a, b in {0, 1},
+                 of device_history_prev with their bilinear weights w.  A tap
+                 is valid when it lies inside the image, its count' > 0, its
+                 e' is finite, |n - n'_q|^2 <= sigma_normal^2, and the surface
+                 test passes: for |n|^2 >= 0.25 the distance of the tap's own
+                 point P'_q = c' + z'_q d'_q / |d'_q| (its pixel-centre ray)
+                 from the plane through P, |n / |n| . (P'_q - P)| <=
+                 sigma_depth r; otherwise (a medium: guide normal 0)
+                 |z'_q - r| <= sigma_depth r.
+     history     Wv = sum of the valid w.  Wv > 0: e_h = sum w e'_q / Wv and
+                 n_h = min(sum w count'_q, max_history) (the count sum is not
+                 renormalised: a partly valid footprint weighs less);
+                 otherwise n_h = 0.
+     blend       e_out = (n_h e_h + n_c e) / (n_h + n_c), 0 when both counts
+                 are 0; device_out = e_out a_d (what rt_denoise_device then
+                 takes as device_rgb with rgb_scale 1 and no tile strata);
+                 history_out col = (e_out, n_h + n_c), the count stored as 0
+                 when h < hit_min or e_out is not finite (a non-finite current
+                 e passes through to device_out); geo = (n, z).
+   All of this is fp64; only the history planes are fp32.  frame_prev and
+   device_history_prev are both NULL when there is no history: then n_h = 0
+   everywhere, device_out = c up to the division and multiplication by a_d,
+   and a first history is written.  The call keeps nothing: device_history_prev
+   is the history committed at the last camera move, every frame at the current
+   pose is computed from it and the current accumulator alone, and on a move
+   the host makes the last frame's device_history_out the next
+   device_history_prev.
+   Asynchronous on hip_stream; needs no rt_scene, allocates nothing; runs on
+   the current device.  device_rgb, device_guides and device_history_prev are
+   only read; device_out may be device_rgb; device_history_out must not overlap
+   device_history_prev, nor device_out either history; histories are 256-B
+   aligned.  RT_ERR_INVALID, before anything is queued: a null frame_now,
+   device_rgb, device_guides, device_history_out or device_out; an empty frame;
+   guide_strata < 1; strata_now < 0 without tile strata; exactly one of
+   frame_prev and device_history_prev NULL; a frame_prev of another size; a
+   misaligned or overlapping history; max_history < 0; a NaN parameter. */
+int rt_temporal_device(const rt_frame *frame_now, const double *device_rgb, double rgb_scale,
+                       const int32_t *device_tile_strata, int32_t strata_now,
+                       const double *device_guides, int32_t guide_strata,
+                       const rt_frame *frame_prev, const void *device_history_prev,
+                       const rt_temporal_params *params, void *device_history_out,
+                       double *device_out, void *hip_stream);
 
 /* ---- tile exchange (multi-GPU tile sharding) ------------------------------ */
 /* Tile-layout chunk partials [tile][chunk][64][3] (rt_render_device with

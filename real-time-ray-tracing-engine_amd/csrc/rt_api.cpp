@@ -1007,6 +1007,56 @@ int rt_denoise_device(const rt_frame *f, const double *device_rgb, double rgb_sc
   return RT_OK;
 }
 
+// ---------------------------------------------------------------- temporal reprojection
+int rt_history_bytes(const rt_frame *f, int64_t *bytes) {
+  int64_t tiles = 0;
+  if (int rc = frame_tiles(f, tiles)) return rc;
+  if (!bytes) return set_err(RT_ERR_INVALID, "null argument");
+  *bytes = (int64_t)rtk_history_bytes(f->image_width, f->image_height);
+  return RT_OK;
+}
+
+int rt_temporal_device(const rt_frame *f, const double *device_rgb, double rgb_scale,
+                       const int32_t *device_tile_strata, int32_t strata_now, const double *device_guides,
+                       int32_t guide_strata, const rt_frame *frame_prev, const void *device_history_prev,
+                       const rt_temporal_params *params, void *device_history_out, double *device_out,
+                       void *hip_stream) {
+  int64_t tiles = 0;
+  if (int rc = frame_tiles(f, tiles)) return rc;
+  if (!device_rgb || !device_guides || !device_history_out || !device_out)
+    return set_err(RT_ERR_INVALID, "null argument");
+  if (guide_strata < 1) return set_err(RT_ERR_INVALID, "guide_strata must be >= 1");
+  if (!device_tile_strata && strata_now < 0) return set_err(RT_ERR_INVALID, "strata_now must be >= 0");
+  if ((frame_prev == nullptr) != (device_history_prev == nullptr))
+    return set_err(RT_ERR_INVALID, "frame_prev and device_history_prev go together: both or neither");
+  if (frame_prev && (frame_prev->image_width != f->image_width || frame_prev->image_height != f->image_height))
+    return set_err(RT_ERR_INVALID, "frame_prev has another size than frame_now");
+  if (((uintptr_t)device_history_out & 255) != 0 || ((uintptr_t)device_history_prev & 255) != 0)
+    return set_err(RT_ERR_INVALID, "a history must be 256-B aligned");
+  {
+    const size_t hb = rtk_history_bytes(f->image_width, f->image_height);
+    const uintptr_t a0 = (uintptr_t)device_history_out, a1 = a0 + hb;
+    const uintptr_t b0 = (uintptr_t)device_history_prev, b1 = b0 + hb;
+    const uintptr_t o0 = (uintptr_t)device_out;
+    const uintptr_t o1 = o0 + (size_t)f->image_width * f->image_height * 3 * sizeof(double);
+    if (device_history_prev && a0 < b1 && b0 < a1)
+      return set_err(RT_ERR_INVALID, "device_history_out overlaps device_history_prev");
+    if ((o0 < a1 && a0 < o1) || (device_history_prev && o0 < b1 && b0 < o1))
+      return set_err(RT_ERR_INVALID, "device_out overlaps a history");
+  }
+  rt_temporal_params q{};
+  if (params) q = *params;
+  if (q.max_history < 0) return set_err(RT_ERR_INVALID, "max_history must be >= 0");
+  const double par[3] = {q.sigma_depth, q.sigma_normal, q.hit_min};
+  for (double v : par)
+    if (v != v) return set_err(RT_ERR_INVALID, "a temporal parameter is NaN");
+  hipError_t e = rtk_launch_temporal(f, device_rgb, rgb_scale, device_tile_strata, strata_now, device_guides,
+                                     guide_strata, frame_prev, device_history_prev, &q, device_history_out,
+                                     device_out, (hipStream_t)hip_stream);
+  if (e != hipSuccess) return hip_err(e, "temporal launch");
+  return RT_OK;
+}
+
 int rt_render_stats(rt_scene *s, const rt_frame *f, const rt_render_params *p,
                     rt_path_stats *stats) {
   if (!s || !stats || !p) return set_err(RT_ERR_INVALID, "null argument");

@@ -1,6 +1,6 @@
 // rt_kernels.h — every rtk_* launcher, declared once: included by the files
 // that define them (rt_kernel.hip, rt_frame.hip, rt_adaptive.hip, rt_guides.hip,
-// rt_denoise.hip, rt_bvh_build.hip, rt_bvh_sah.hip) and by their caller (rt_api.cpp), so a
+// rt_denoise.hip, rt_temporal.hip, rt_bvh_build.hip, rt_bvh_sah.hip) and by their caller (rt_api.cpp), so a
 // definition whose parameter list drifts from its callers' no longer compiles.
 #ifndef RT_KERNELS_H
 #define RT_KERNELS_H
@@ -59,6 +59,14 @@ hipError_t rtk_launch_denoise(int W, int H, const double *rgb, double scale, con
                               const double *guides, int guide_strata, int passes, double sigma_n,
                               double sigma_z, double sigma_h, double sigma_c, void *workspace, double *out,
                               hipStream_t stream);
+
+// ---- rt_temporal.hip: the temporal reprojection (params checked, may be null; prev /
+// history_prev both null: no history)
+size_t rtk_history_bytes(int W, int H);
+hipError_t rtk_launch_temporal(const rt_frame *now, const double *rgb, double scale, const int32_t *tile_strata,
+                               int strata_now, const double *guides, int guide_strata, const rt_frame *prev,
+                               const void *history_prev, const rt_temporal_params *params, void *history_out,
+                               double *out, hipStream_t stream);
 
 // ---- rt_bvh_build.hip, rt_bvh_sah.hip: the device BVH builders
 size_t rtk_lbvh_temp_bytes(int n);

@@ -172,6 +172,32 @@ def denoise_params(p=None):
     return out
 
 
+class TemporalParams(C.Structure):
+    """rt_temporal_params: zero-filled = every default (include/rt_api.h
+    RT_TEMPORAL_*); a negative sigma switches its test off, a negative hit_min
+    admits every pixel."""
+    _fields_ = [("max_history", C.c_int32), ("reserved", C.c_int32),
+                ("sigma_depth", C.c_double), ("sigma_normal", C.c_double), ("hit_min", C.c_double)]
+
+
+# include/rt_api.h RT_TEMPORAL_*: the shipped defaults (tests/test_temporal.py
+# reads the header's values and compares)
+RT_TEMPORAL_MAX_HISTORY = 64
+RT_TEMPORAL_SIGMA_DEPTH, RT_TEMPORAL_SIGMA_NORMAL, RT_TEMPORAL_HIT_MIN = 0.5, -1.0, 0.75
+
+
+def temporal_params(p=None):
+    """A TemporalParams from None (the defaults), a TemporalParams, or a dict of its fields."""
+    if p is None or isinstance(p, TemporalParams):
+        return p
+    out = TemporalParams()
+    for k, v in dict(p).items():
+        if k not in dict(TemporalParams._fields_):
+            raise KeyError("unknown rt_temporal_params field %r" % k)
+        setattr(out, k, v)
+    return out
+
+
 def tuning(t=None):
     """A Tuning from None (the default), a Tuning, or a dict of its fields."""
     if t is None or isinstance(t, Tuning):
@@ -195,4 +221,5 @@ EXPORTS = (
     "rt_render_tiles_device", "rt_adaptive_update_device", "rt_adaptive_select_device",
     "rt_to_bytes_tiles_device",
     "rt_render_guides_device", "rt_denoise_workspace_bytes", "rt_denoise_device",
+    "rt_history_bytes", "rt_temporal_device",
 )

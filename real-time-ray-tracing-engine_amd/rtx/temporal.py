@@ -1,0 +1,369 @@
+"""Temporal reprojection: the display keeps its history across camera moves.
+
+rtx.progressive, rtx.adaptive and rtx.denoise clear everything when the camera
+moves, as the reference does, and the viewer is back at 1-spp noise behind the
+filter.  Here the image displayed at the previous pose is carried into the new
+pose wherever the same first-hit surface is still visible, and blended with
+the new pose's samples by sample count (rt_temporal_device); the a-trous filter
+then runs on the blend.  The fp64 accumulator stays the source of truth and is
+only read; the library keeps no state.
+
+A history is two fp32 float4 planes of the frame's size, each padded to 256 B:
+col = (e.r, e.g, e.b, count), geo = (n.x, n.y, n.z, z).  It always travels
+with the rt_frame it was taken at.
+
+The definition (NumpyOps.temporal, fp64).  With the filter's quantities (see
+rtx.denoise: c, a_d = max(albedo / g, 0.01), e = c / a_d, n, h, z) and the
+current count n_c = strata_now, or with tile_strata the pixel's tile's strata,
+per pixel p = (i, j):
+
+ 1. position: d = pixel00_loc + i pixel_delta_u + j pixel_delta_v - center,
+    P = center + z d / |d|.  This is the pixel-centre ray; z is the mean
+    first-hit distance of jittered (and, with defocus, lens-sampled) rays, so
+    with jitter or defocus P is an approximation of where the samples hit.
+ 2. projection into the previous frame (c', pixel00', du', dv'): v = P - c',
+    N' = du' x dv', num = (pixel00' - c') . N', den = v . N'.  History is
+    possible only if den num > 0 (P in front of the previous camera) and
+    h >= hit_min.  q = c' + (num / den) v - pixel00', x = q . du' / du' . du',
+    y = q . dv' / dv' . dv', r = |v|.
+ 3. four bilinear taps (floor x + a, floor y + b), a, b in {0, 1}, weight w.
+    A tap is valid when it lies inside the image, its count' > 0, its e' is
+    finite, |n - n'_q|^2 <= sigma_normal^2, and the surface test passes: with
+    |n|^2 >= 0.25, P'_q = c' + z'_q d'_q / |d'_q| (the tap's own pixel-centre
+    ray) lies within sigma_depth r of the plane through P with normal n / |n|
+    (a plane distance: a surface seen at a grazing angle survives, where a
+    plain depth difference between neighbouring pixels would not); with
+    |n|^2 < 0.25 (a medium: its guide normal is 0) |z'_q - r| <= sigma_depth r.
+ 4. Wv = sum of the valid w.  Wv > 0: e_h = sum w e'_q / Wv,
+    n_h = min(sum w count'_q, max_history) -- the count sum is not
+    renormalised, so a partly valid footprint weighs less and Wv needs no
+    threshold.  Otherwise n_h = 0.
+ 5. e_out = (n_h e_h + n_c e) / (n_h + n_c), 0 when both counts are 0;
+    out = e_out a_d -- what rt_denoise_device takes as device_rgb with
+    rgb_scale 1 and no tile strata.  history_out: col = fp32(e_out, n_h + n_c),
+    the count stored as 0 when h < hit_min or e_out is not finite (a
+    non-finite current e passes through to out); geo = fp32(n, z).
+ 6. without a previous history n_h = 0 everywhere, out = c up to the division
+    and multiplication by a_d, and a first history is written.
+
+Stateless by construction: history_prev is the snapshot committed at the last
+camera move; every displayed frame at the current pose is computed from it and
+the current accumulator, so nothing compounds from frame to frame.  On a move
+the host swaps: the last displayed frame's history_out becomes history_prev
+(TemporalDisplay.reset).
+
+Out of scope: moving spheres get no motion vectors (their blur is already in
+every frame's time average), and reflections and refractions are reprojected
+at their first-hit point; max_history bounds how long either can lag.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import abi
+from .denoise import DenoisedDisplay
+from .denoise import NumpyOps as _FilterOps
+from .lib import check, load
+
+
+def resolve(params=None):
+    """(max_history, sigma_depth, sigma_normal, hit_min) of None / a dict / an
+    abi.TemporalParams: 0 = the default, a sigma < 0 = its test off (returned
+    as None)."""
+    p = abi.temporal_params(params) or abi.TemporalParams()
+    if p.max_history < 0:
+        raise ValueError("max_history must be >= 0")
+
+    def pick(v, d):
+        return d if v == 0 else float(v)
+
+    sz = pick(p.sigma_depth, abi.RT_TEMPORAL_SIGMA_DEPTH)
+    sn = pick(p.sigma_normal, abi.RT_TEMPORAL_SIGMA_NORMAL)
+    return (float(p.max_history or abi.RT_TEMPORAL_MAX_HISTORY), None if sz < 0 else sz, None if sn < 0 else sn,
+            pick(p.hit_min, abi.RT_TEMPORAL_HIT_MIN))
+
+
+def history_bytes(frame):
+    """rt_history_bytes: two float4 planes, each padded to 256 B."""
+    return 2 * ((frame.image_width * frame.image_height * 16 + 255) & ~255)
+
+
+def pack_history(frame, history):
+    """(col, geo) float32 [H, W, 4] arrays -> the device layout, a uint8 array of history_bytes."""
+    n = frame.image_width * frame.image_height * 16
+    buf = np.zeros(history_bytes(frame), dtype=np.uint8)
+    for k, a in enumerate(history):
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        buf[k * (len(buf) // 2):k * (len(buf) // 2) + n] = a.reshape(-1).view(np.uint8)
+    return buf
+
+
+def unpack_history(frame, buf):
+    """The device layout -> (col, geo) float32 [H, W, 4]."""
+    h, w = frame.image_height, frame.image_width
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    half = len(buf) // 2
+    return tuple(buf[k * half:k * half + h * w * 16].view(np.float32).reshape(h, w, 4).copy() for k in range(2))
+
+
+def _cam(frame):
+    def v(a):
+        return np.array([a.x, a.y, a.z], dtype=np.float64)
+    return v(frame.center), v(frame.pixel00_loc), v(frame.pixel_delta_u), v(frame.pixel_delta_v)
+
+
+def _dot(a, b):
+    return a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1] + a[..., 2] * b[..., 2]
+
+
+def _centre_points(cam, ii, jj, z):
+    """c + z d / |d| along the pixel-centre rays of pixels (ii, jj)."""
+    c, p00, du, dv = cam
+    d = p00 + ii[..., None] * du + jj[..., None] * dv - c
+    with np.errstate(invalid="ignore", over="ignore"):
+        return c + (z / np.sqrt(_dot(d, d)))[..., None] * d
+
+
+def _pixel_tiles(tile_strata, frame):
+    tx, ty = (frame.image_width + 7) // 8, (frame.image_height + 7) // 8
+    s = np.maximum(0, np.asarray(tile_strata)).astype(np.float64).reshape(ty, tx)
+    return np.repeat(np.repeat(s, 8, axis=0), 8, axis=1)[:frame.image_height, :frame.image_width]
+
+
+class NumpyOps:
+    """rt_temporal_device on host arrays, in fp64: the statement of record."""
+
+    def history_bytes(self, frame):
+        return history_bytes(frame)
+
+    def temporal(self, frame_now, rgb, scale, tile_strata, strata_now, guides, guide_strata, frame_prev=None,
+                 history_prev=None, params=None):
+        """-> (out [H, W, 3] float64, (col, geo) float32 [H, W, 4] each, margin [H, W]).
+
+        margin: the smallest |lhs - rhs| / rhs over the surface and normal
+        comparisons of the pixel's taps with w > 1e-6 (inf where it has none):
+        a pixel with a tiny margin sits on a threshold, where another rounding
+        of the same arithmetic may decide the other way."""
+        if guide_strata < 1:
+            raise ValueError("guide_strata must be >= 1")
+        if (frame_prev is None) != (history_prev is None):
+            raise ValueError("frame_prev and history_prev go together")
+        mh, sz, sn, hmin = resolve(params)
+        H, W = frame_now.image_height, frame_now.image_width
+        e, a_d, n, z, h = _FilterOps().prepare(frame_now, rgb, scale, tile_strata, guides, guide_strata)
+        n_c = _pixel_tiles(tile_strata, frame_now) if tile_strata is not None else np.full((H, W), float(strata_now))
+        n_h, e_h, margin = np.zeros((H, W)), np.zeros((H, W, 3)), np.full((H, W), np.inf)
+        if history_prev is not None:
+            if (frame_prev.image_width, frame_prev.image_height) != (W, H):
+                raise ValueError("frame_prev has another size than frame_now")
+            col, geo = (np.asarray(a, dtype=np.float64) for a in history_prev)
+            jj, ii = np.mgrid[0:H, 0:W]
+            prev = _cam(frame_prev)
+            cp, p00p, dup, dvp = prev
+            P = _centre_points(_cam(frame_now), ii, jj, z)
+            v = P - cp
+            Np = np.cross(dup, dvp)
+            num, den = _dot(p00p - cp, Np), _dot(v, Np)
+            with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+                q = cp + (num / den)[..., None] * v - p00p
+                x, y = _dot(q, dup) / _dot(dup, dup), _dot(q, dvp) / _dot(dvp, dvp)
+                possible = (den * num > 0) & (h >= hmin) & (x > -1) & (x < W) & (y > -1) & (y < H)
+            x, y = np.where(possible, x, 0.0), np.where(possible, y, 0.0)
+            fx, fy = np.floor(x), np.floor(y)
+            x0, y0, wx, wy = fx.astype(np.int64), fy.astype(np.int64), x - fx, y - fy
+            r = np.sqrt(_dot(v, v))
+            nn = _dot(n, n)
+            plane = nn >= 0.25
+            nu = (1.0 / np.sqrt(np.where(plane, nn, 1.0)))[..., None] * n
+            Wv, cnt, se = np.zeros((H, W)), np.zeros((H, W)), np.zeros((H, W, 3))
+            for b in (0, 1):
+                for a in (0, 1):
+                    qx, qy = x0 + a, y0 + b
+                    inside = possible & (qx >= 0) & (qx < W) & (qy >= 0) & (qy < H)
+                    cx, cy = np.clip(qx, 0, W - 1), np.clip(qy, 0, H - 1)
+                    w = (wx if a else 1.0 - wx) * (wy if b else 1.0 - wy)
+                    cq, gq = col[cy, cx], geo[cy, cx]
+                    ok = inside & (cq[..., 3] > 0) & np.isfinite(cq[..., :3]).all(-1)
+                    near = inside & (w > 1e-6)
+                    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+                        if sn is not None:
+                            dn = n - gq[..., :3]
+                            lhs = _dot(dn, dn)
+                            ok &= lhs <= sn * sn
+                            margin = np.fmin(margin, np.where(near, np.abs(lhs - sn * sn) / (sn * sn), np.inf))
+                        if sz is not None:
+                            Pq = _centre_points(prev, cx, cy, gq[..., 3])
+                            dist = np.where(plane, np.abs(_dot(nu, Pq - P)), np.abs(gq[..., 3] - r))
+                            ok &= dist <= sz * r
+                            margin = np.fmin(margin, np.where(near, np.abs(dist - sz * r) / (sz * r), np.inf))
+                    w = np.where(ok, w, 0.0)
+                    Wv += w
+                    cnt += w * np.where(ok, cq[..., 3], 0.0)
+                    se += w[..., None] * np.where(ok[..., None], cq[..., :3], 0.0)
+            some = Wv > 0
+            n_h = np.where(some, np.minimum(cnt, mh), 0.0)
+            e_h = np.where(some[..., None], se / np.where(some, Wv, 1.0)[..., None], 0.0)
+        total = n_h + n_c
+        with np.errstate(invalid="ignore", over="ignore"):
+            e_out = (n_h[..., None] * e_h + n_c[..., None] * e) / np.where(total > 0, total, 1.0)[..., None]
+            e_out = np.where((total > 0)[..., None], e_out, 0.0)
+            out = e_out * a_d
+            count = np.where((h >= hmin) & np.isfinite(e_out).all(-1), total, 0.0)
+            col_out = np.concatenate([e_out, count[..., None]], axis=-1).astype(np.float32)
+            geo_out = np.concatenate([n, z[..., None]], axis=-1).astype(np.float32)
+        return out, (col_out, geo_out), margin
+
+
+class HipOps:
+    """rt_history_bytes / rt_temporal_device on torch CUDA tensors, on one stream."""
+
+    def __init__(self, device, stream):
+        import torch
+        self.torch = torch
+        self.device = device
+        self.stream = stream
+        self.lib = load()
+
+    def history_bytes(self, frame):
+        n = C.c_int64(0)
+        check(self.lib.rt_history_bytes(C.byref(frame), C.byref(n)))
+        return n.value
+
+    def history(self, frame):
+        """A history tensor for `frame` (torch allocations are 512-B aligned)."""
+        t = self.torch
+        with t.cuda.stream(self.stream):
+            return t.empty((self.history_bytes(frame),), dtype=t.uint8, device=self.device)
+
+    def temporal(self, frame_now, rgb, scale, tile_strata, strata_now, guides, guide_strata, frame_prev=None,
+                 history_prev=None, params=None, history_out=None, out=None):
+        """-> (out [H, W, 3] float64, history_out uint8), both CUDA tensors."""
+        t = self.torch
+        if history_out is None:
+            history_out = self.history(frame_now)
+        if out is None:
+            with t.cuda.stream(self.stream):
+                out = t.empty((frame_now.image_height, frame_now.image_width, 3), dtype=t.float64,
+                              device=self.device)
+        p = abi.temporal_params(params)
+        check(self.lib.rt_temporal_device(
+            C.byref(frame_now), C.c_void_p(rgb.data_ptr()), C.c_double(scale),
+            C.c_void_p(tile_strata.data_ptr() if tile_strata is not None else 0), int(strata_now),
+            C.c_void_p(guides.data_ptr()), int(guide_strata),
+            C.byref(frame_prev) if frame_prev is not None else None,
+            C.c_void_p(history_prev.data_ptr() if history_prev is not None else 0),
+            C.byref(p) if p is not None else None, C.c_void_p(history_out.data_ptr()),
+            C.c_void_p(out.data_ptr()), C.c_void_p(self.stream.cuda_stream)))
+        return out, history_out
+
+
+class TemporalDisplay:
+    """The reprojected (and, with `filter`, a-trous-filtered) display of a
+    progressive.for_renderer ProgressiveRenderer or an adaptive.for_renderer
+    AdaptiveRenderer `pr`.
+
+    It drives a DenoisedDisplay over `pr` for the guides, their catch-up, the
+    filter and the bytes.  image() blends the current accumulator with the
+    history committed at the last camera move and, with `filter`, passes the
+    blend through rt_denoise_device (`denoise`: its rt_denoise_params).
+    reset(frame) is the camera move: the last displayed frame's history and
+    its rt_frame are committed, the wrapped renderer and the guides restart,
+    and the history is kept; a frame of another size drops it.  clear()
+    forgets the history (a scene change).  Two histories, the blend and
+    DenoisedDisplay's buffers are allocated once per frame size.
+
+        td = TemporalDisplay(progressive.for_renderer(R, frame, seed=5))
+        pipe = progressive.DisplayPipeline(td, bytes_fn=td.bytes_into)
+    """
+
+    def __init__(self, pr, guide_strata=16, params=None, denoise=None, filter=True):
+        self.dd = DenoisedDisplay(pr, guide_strata=guide_strata, params=denoise)
+        self.pr = pr
+        self.torch = self.dd.torch
+        self.stream = pr.stream
+        self.params = abi.temporal_params(params)
+        self.filter = bool(filter)
+        self.ops = HipOps(pr.acc.device, self.stream)
+        self._adaptive = self.dd._adaptive
+        self._allocate()
+
+    def _allocate(self):
+        t, f = self.torch, self.pr.frame
+        self.hist = [self.ops.history(f), self.ops.history(f)]  # [0]: committed (prev), [1]: the displayed frame's
+        with t.cuda.stream(self.stream):
+            self.blend = t.empty((f.image_height, f.image_width, 3), dtype=t.float64, device=self.pr.acc.device)
+        self._shape = (f.image_width, f.image_height)
+        self.frame_prev = None   # the rt_frame hist[0] was taken at; None: no history
+        self._shown = None       # the rt_frame hist[1] was written at by the last image()
+
+    # what DisplayPipeline reads of a renderer
+    @property
+    def acc(self):
+        return self.pr.acc
+
+    @property
+    def frame(self):
+        return self.pr.frame
+
+    @property
+    def samples_taken(self):
+        return self.dd.samples_taken
+
+    @property
+    def converged(self):
+        return self.dd.converged
+
+    @property
+    def guides(self):
+        return self.dd.guides
+
+    @property
+    def guides_done(self):
+        return self.dd.guides_done
+
+    @property
+    def has_history(self):
+        return self.frame_prev is not None
+
+    def step(self, n=1):
+        """Steps the wrapped renderer and its guides; returns the strata traced."""
+        return self.dd.step(n)
+
+    def blended(self):
+        """The blend alone ([H, W, 3] float64 CUDA tensor); writes the displayed frame's history."""
+        dd, pr = self.dd, self.pr
+        dd._catch_up()
+        self.ops.temporal(pr.frame, pr.acc, 1.0 if self._adaptive else pr.scale,
+                          pr.tile_strata if self._adaptive else None, self.samples_taken, dd.guides,
+                          max(1, dd.guides_done), self.frame_prev, self.hist[0] if self.has_history else None,
+                          self.params, self.hist[1], self.blend)
+        self._shown = abi.Frame.from_buffer_copy(pr.frame)
+        return self.blend
+
+    def image(self):
+        img = self.blended()
+        if not self.filter:
+            return img
+        dd = self.dd
+        return dd.ops.denoise(self.pr.frame, img, 1.0, None, dd.guides, max(1, dd.guides_done), dd.params,
+                              dd.workspace, dd.out)
+
+    def bytes(self, out=None):
+        return self.dd.ops.bytes(self.image(), out)
+
+    def bytes_into(self, pr, out):
+        """DisplayPipeline's bytes_fn: the displayed frame's bytes into `out`."""
+        return self.bytes(out)
+
+    def reset(self, frame=None):
+        """Camera moved: commit the last displayed frame's history, restart the renderer and the guides."""
+        if self._shown is not None:
+            self.hist.reverse()
+            self.frame_prev, self._shown = self._shown, None
+        self.dd.reset(frame)
+        if (self.pr.frame.image_width, self.pr.frame.image_height) != self._shape:
+            self._allocate()
+
+    def clear(self):
+        """Forget the history (the scene changed): the next frames start from the samples alone."""
+        self.frame_prev = self._shown = None
