@@ -45,6 +45,10 @@
  *                     <- no counterpart: DynamicCamera displays the raw accumulation
  *                        (DynamicCamera.cpp:284-300); these give the display first-hit
  *                        albedo / normal / depth sums and an edge-avoiding filter over them
+ *   rt_denoise_variance_workspace_bytes / rt_denoise_variance_device
+ *                     <- no counterpart: the same filter steered by the variance of each pixel's
+ *                        estimate (the adaptive sampler's moments, or a spatial estimate), so
+ *                        that it narrows as the frame converges
  *   rt_history_bytes / rt_temporal_device
  *                     <- no counterpart: DynamicCamera clears its accumulation when the camera
  *                        moves (DynamicCamera.cpp:269-276); these reproject the previous pose's
@@ -607,6 +611,78 @@ int rt_denoise_device(const rt_frame *frame, const double *device_rgb, double rg
                       const int32_t *device_tile_strata, const double *device_guides, int32_t guide_strata,
                       const rt_denoise_params *params, void *device_workspace, double *device_out,
                       void *hip_stream);
+
+/* ---- variance-guided display filter (functions and one struct added under
+   ABI 5: no struct or signature above changed) --------------------------------
+   rt_denoise_device's colour term is normalised by the pixel's own luminance:
+   it blurs a converged frame as much as a noisy one.  This second entry point
+   normalises by the standard deviation of the pixel's estimate, so the filter
+   narrows as the estimate converges (rtx/denoise.py states it in NumPy,
+   NumpyOps.denoise_variance; DESIGN.md "Variance-guided display filter"). */
+
+/* The filter's own defaults: sigma_lum is the best point of the sweep of
+   tools/variance_bench.py (DESIGN.md records it); passes, sigma_normal,
+   sigma_depth and sigma_hit default to RT_DENOISE_* above. */
+#define RT_DENOISE_SIGMA_LUM 4.0
+#define RT_DENOISE_MIN_BATCHES 4
+
+typedef struct rt_denoise_variance_params {
+  int32_t passes;      /* as rt_denoise_params.passes */
+  int32_t min_batches; /* batches a tile needs before its moments are used; 0: RT_DENOISE_MIN_BATCHES;
+                          anything else below 2 counts as 2 */
+  double sigma_normal; /* 0: default; < 0: term off */
+  double sigma_depth;  /* 0: default; < 0: term off */
+  double sigma_hit;    /* 0: default; < 0: term off */
+  double sigma_lum;    /* 0: default; < 0: term off; not halved per pass (the variance shrinks instead) */
+} rt_denoise_variance_params;
+
+/* Bytes of workspace rt_denoise_variance_device needs for this frame (a
+   multiple of 256): four fp32 float4 planes and one float plane, each padded
+   to 256 B, 68 B per pixel -- col[0], col[1] = (e.r, e.g, e.b, v), geo, alb
+   as rt_denoise_device's, and h. */
+int rt_denoise_variance_workspace_bytes(const rt_frame *frame, int64_t *bytes);
+
+/* rt_denoise_device with its colour term replaced.  c, a_d, e, n, h, z and y
+   are that function's.  Per pixel a variance v of the luminance of e:
+     from moments  when device_s1 and device_s2 are given ([H][W] doubles as
+                   rt_adaptive_update_device maintains them, with
+                   device_tile_strata and batch_strata >= 1) and the pixel's
+                   tile has b = tile_strata[t] / batch_strata >= min_batches
+                   batches (integer division):
+                   v_c = max(0, (s2 - s1 s1 / b) / (b - 1)) / b and
+                   v = v_c / lum(a_d)^2, lum the Rec. 709 luminance.  Dividing
+                   the variance of c's luminance by lum(a_d)^2 gives the
+                   variance of e's luminance exactly for a grey albedo only;
+                   for a coloured albedo it is an approximation.
+     spatial       everywhere else: over the 7x7 window at step 1, tap weights
+                   exp(-min(x, 80)) with x the normal, depth and hit terms of
+                   rt_denoise_device (s = 1, d = max(|di|, |dj|)), the centre
+                   1, taps outside the image or with a non-finite e skipped;
+                   with d_q = y_q - y_p: m1 = sum w d / sum w,
+                   m2 = sum w d^2 / sum w, v = max(0, m2 - m1^2) -- the weighted
+                   variance of y over the window (the shift by y_p drops out).
+     v = 0 where e is not finite.
+   Passes as rt_denoise_device's (B3 taps, step 2^k, the normal, depth and hit
+   terms, the NaN rules) with the colour term |y_p - y_q| / (sigma_lum
+   sqrt(v~_p) + 1e-6), v~_p the 3x3 Gaussian (1/4, 1/2, 1/4 per axis, step 1)
+   of the pass's input v over the in-image pixels whose e is finite,
+   renormalised.  The variance is filtered with the colour:
+   v'_p = sum w^2 v_q / (sum w)^2, or v_p when sum w = 0.  out = e a_d;
+   device_variance_out ([H][W] doubles), unless NULL, takes the final v.
+   With sigma_lum < 0 the result is rt_denoise_device's with sigma_color < 0.
+   The contracts are rt_denoise_device's: no rt_scene, nothing allocated, no
+   state kept, inputs only read, device_out may be device_rgb, the workspace
+   256-B aligned.  RT_ERR_INVALID before anything is queued: everything
+   rt_denoise_device refuses; exactly one of device_s1 / device_s2 NULL;
+   moments without device_tile_strata or with batch_strata < 1; a
+   device_variance_out that overlaps the workspace or device_out; a NaN
+   parameter. */
+int rt_denoise_variance_device(const rt_frame *frame, const double *device_rgb, double rgb_scale,
+                               const int32_t *device_tile_strata, const double *device_guides,
+                               int32_t guide_strata, const double *device_s1, const double *device_s2,
+                               int32_t batch_strata, const rt_denoise_variance_params *params,
+                               void *device_workspace, double *device_out, double *device_variance_out,
+                               void *hip_stream);
 
 /* ---- temporal reprojection (functions added under ABI 5: no struct or
    signature above changed) --------------------------------------------------

@@ -1007,6 +1007,62 @@ int rt_denoise_device(const rt_frame *f, const double *device_rgb, double rgb_sc
   return RT_OK;
 }
 
+int rt_denoise_variance_workspace_bytes(const rt_frame *f, int64_t *bytes) {
+  int64_t tiles = 0;
+  if (int rc = frame_tiles(f, tiles)) return rc;
+  if (!bytes) return set_err(RT_ERR_INVALID, "null argument");
+  *bytes = (int64_t)rtk_denoise_variance_workspace_bytes(f->image_width, f->image_height);
+  return RT_OK;
+}
+
+int rt_denoise_variance_device(const rt_frame *f, const double *device_rgb, double rgb_scale,
+                               const int32_t *device_tile_strata, const double *device_guides,
+                               int32_t guide_strata, const double *device_s1, const double *device_s2,
+                               int32_t batch_strata, const rt_denoise_variance_params *params,
+                               void *device_workspace, double *device_out, double *device_variance_out,
+                               void *hip_stream) {
+  int64_t tiles = 0;
+  if (int rc = frame_tiles(f, tiles)) return rc;
+  if (!device_rgb || !device_guides || !device_workspace || !device_out)
+    return set_err(RT_ERR_INVALID, "null argument");
+  if (guide_strata < 1) return set_err(RT_ERR_INVALID, "guide_strata must be >= 1");
+  if ((device_s1 == nullptr) != (device_s2 == nullptr))
+    return set_err(RT_ERR_INVALID, "device_s1 and device_s2 go together: both or neither");
+  if (device_s1 && !device_tile_strata) return set_err(RT_ERR_INVALID, "moments need device_tile_strata");
+  if (device_s1 && batch_strata < 1) return set_err(RT_ERR_INVALID, "moments need batch_strata >= 1");
+  if (((uintptr_t)device_workspace & 255) != 0) return set_err(RT_ERR_INVALID, "workspace must be 256-B aligned");
+  {
+    const size_t px = (size_t)f->image_width * f->image_height;
+    const uintptr_t w0 = (uintptr_t)device_workspace;
+    const uintptr_t w1 = w0 + rtk_denoise_variance_workspace_bytes(f->image_width, f->image_height);
+    const uintptr_t o0 = (uintptr_t)device_out, o1 = o0 + px * 3 * sizeof(double);
+    const uintptr_t v0 = (uintptr_t)device_variance_out, v1 = v0 + px * sizeof(double);
+    if (o0 < w1 && w0 < o1) return set_err(RT_ERR_INVALID, "device_out overlaps the workspace");
+    if (device_variance_out && v0 < w1 && w0 < v1)
+      return set_err(RT_ERR_INVALID, "device_variance_out overlaps the workspace");
+    if (device_variance_out && v0 < o1 && o0 < v1)
+      return set_err(RT_ERR_INVALID, "device_variance_out overlaps device_out");
+  }
+  rt_denoise_variance_params q{};
+  if (params) q = *params;
+  if (q.passes > RT_DENOISE_MAX_PASSES)
+    return set_err(RT_ERR_INVALID, "passes must be at most " + std::to_string(RT_DENOISE_MAX_PASSES));
+  const double sig[4] = {q.sigma_normal, q.sigma_depth, q.sigma_hit, q.sigma_lum};
+  for (double v : sig)
+    if (v != v) return set_err(RT_ERR_INVALID, "a sigma is NaN");
+  auto pick = [](double v, double dflt) { return v == 0.0 ? dflt : v; }; // < 0: off
+  const int passes = q.passes == 0 ? RT_DENOISE_PASSES : q.passes;
+  const int min_batches = std::max(2, q.min_batches == 0 ? RT_DENOISE_MIN_BATCHES : q.min_batches);
+  hipError_t e = rtk_launch_denoise_variance(
+      f->image_width, f->image_height, device_rgb, rgb_scale, device_tile_strata, device_guides, guide_strata,
+      device_s1, device_s2, batch_strata, min_batches, passes, pick(q.sigma_normal, RT_DENOISE_SIGMA_NORMAL),
+      pick(q.sigma_depth, RT_DENOISE_SIGMA_DEPTH), pick(q.sigma_hit, RT_DENOISE_SIGMA_HIT),
+      pick(q.sigma_lum, RT_DENOISE_SIGMA_LUM), device_workspace, device_out, device_variance_out,
+      (hipStream_t)hip_stream);
+  if (e != hipSuccess) return hip_err(e, "variance-guided denoise launch");
+  return RT_OK;
+}
+
 // ---------------------------------------------------------------- temporal reprojection
 int rt_history_bytes(const rt_frame *f, int64_t *bytes) {
   int64_t tiles = 0;

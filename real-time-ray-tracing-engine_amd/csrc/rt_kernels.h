@@ -60,6 +60,15 @@ hipError_t rtk_launch_denoise(int W, int H, const double *rgb, double scale, con
                               double sigma_z, double sigma_h, double sigma_c, void *workspace, double *out,
                               hipStream_t stream);
 
+// the variance-guided filter: s1 / s2 null = no moments; min_batches resolved (>= 2); sigma_l <= 0: term off;
+// var_out may be null
+size_t rtk_denoise_variance_workspace_bytes(int W, int H);
+hipError_t rtk_launch_denoise_variance(int W, int H, const double *rgb, double scale, const int32_t *tile_strata,
+                                       const double *guides, int guide_strata, const double *s1, const double *s2,
+                                       int batch_strata, int min_batches, int passes, double sigma_n,
+                                       double sigma_z, double sigma_h, double sigma_l, void *workspace,
+                                       double *out, double *var_out, hipStream_t stream);
+
 // ---- rt_temporal.hip: the temporal reprojection (params checked, may be null; prev /
 // history_prev both null: no history)
 size_t rtk_history_bytes(int W, int H);

@@ -172,6 +172,32 @@ def denoise_params(p=None):
     return out
 
 
+class DenoiseVarianceParams(C.Structure):
+    """rt_denoise_variance_params: zero-filled = every default (include/rt_api.h
+    RT_DENOISE_*); a negative sigma switches its term off, passes < 0 the
+    filter; min_batches below 2 counts as 2."""
+    _fields_ = [("passes", C.c_int32), ("min_batches", C.c_int32),
+                ("sigma_normal", C.c_double), ("sigma_depth", C.c_double),
+                ("sigma_hit", C.c_double), ("sigma_lum", C.c_double)]
+
+
+# include/rt_api.h: the variance-guided filter's own defaults (tests/test_variance.py
+# reads the header's values and compares)
+RT_DENOISE_SIGMA_LUM, RT_DENOISE_MIN_BATCHES = 4.0, 4
+
+
+def denoise_variance_params(p=None):
+    """A DenoiseVarianceParams from None (the defaults), a DenoiseVarianceParams, or a dict of its fields."""
+    if p is None or isinstance(p, DenoiseVarianceParams):
+        return p
+    out = DenoiseVarianceParams()
+    for k, v in dict(p).items():
+        if k not in dict(DenoiseVarianceParams._fields_):
+            raise KeyError("unknown rt_denoise_variance_params field %r" % k)
+        setattr(out, k, v)
+    return out
+
+
 class TemporalParams(C.Structure):
     """rt_temporal_params: zero-filled = every default (include/rt_api.h
     RT_TEMPORAL_*); a negative sigma switches its test off, a negative hit_min
@@ -222,4 +248,5 @@ EXPORTS = (
     "rt_to_bytes_tiles_device",
     "rt_render_guides_device", "rt_denoise_workspace_bytes", "rt_denoise_device",
     "rt_history_bytes", "rt_temporal_device",
+    "rt_denoise_variance_workspace_bytes", "rt_denoise_variance_device",
 )

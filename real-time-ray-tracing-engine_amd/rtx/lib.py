@@ -79,6 +79,11 @@ def load():
     L.rt_temporal_device.argtypes = [P(abi.Frame), C.c_void_p, C.c_double, C.c_void_p, C.c_int32, C.c_void_p,
                                      C.c_int32, P(abi.Frame), C.c_void_p, P(abi.TemporalParams), C.c_void_p,
                                      C.c_void_p, C.c_void_p]
+    L.rt_denoise_variance_workspace_bytes.argtypes = [P(abi.Frame), P(C.c_int64)]
+    L.rt_denoise_variance_device.argtypes = [P(abi.Frame), C.c_void_p, C.c_double, C.c_void_p, C.c_void_p,
+                                             C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                             P(abi.DenoiseVarianceParams), C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p]
     for name in abi.EXPORTS:
         getattr(L, name).restype = C.c_char_p if name == "rt_last_error" else C.c_int
     if L.rt_abi_version() != abi.RT_ABI_VERSION:
