@@ -778,6 +778,73 @@ int rt_temporal_device(const rt_frame *frame_now, const double *device_rgb, doub
                        const rt_temporal_params *params, void *device_history_out,
                        double *device_out, void *hip_stream);
 
+/* ---- temporal variance (functions added under ABI 5: no struct or signature
+   above changed) ------------------------------------------------------------
+   The two stages above composed: the variance of the displayed estimate is
+   carried across camera moves with its colour, and the variance-guided filter
+   runs on the blend with that variance, so a blend that holds 64 strata of
+   history is filtered as a 64-strata frame and not as a 1-stratum one
+   (rtx/temporal.py NumpyOps.temporal_variance and rtx/denoise.py
+   NumpyOps.denoise_given_variance state both in NumPy; DESIGN.md "Temporal
+   variance").  v is the variance of the Rec. 709 luminance of e = c / a_d, the
+   unit of rt_denoise_variance_device. */
+
+/* Bytes of one variance history for this frame (a multiple of 256): a history
+   with a third plane -- col, geo (fp32 float4) at the offsets rt_history_bytes
+   gives them, then var (fp32 scalars), each padded to 256 B, 36 B per pixel.
+   Its first rt_history_bytes bytes are a plain history. */
+int rt_history_variance_bytes(const rt_frame *frame, int64_t *bytes);
+
+/* rt_temporal_device on variance histories.  Position, projection, the four
+   taps and their validity, Wv, e_h, n_h, n_c, e_out, device_out, col and geo
+   are that function's, bit for bit.  Added, per pixel p:
+     current     v_c = device_variance_now[p] ([H][W] doubles), or 0 when that
+                 is NaN or negative.
+     history     Wv > 0: v_h = sum w max(v'_q, 0) / Wv over the valid taps (the
+                 same validity; a NaN v'_q counts as 0, and a tap of weight 0
+                 adds nothing, an infinite v'_q included).  Linear on purpose, not
+                 sum w^2 v' / Wv^2: after one reprojection neighbouring history
+                 pixels share taps and are correlated, crediting the
+                 interpolation with a variance reduction would compound over
+                 moves, and an overestimate only keeps the filter wider.
+                 max_history caps n_h and leaves v_h alone.
+     blend       with a = n_h / total, b = n_c / total, total = n_h + n_c:
+                 v_out = a^2 v_h + b^2 v_c; a term whose count is 0 is dropped,
+                 not multiplied; v_out = 0 when total = 0; without history
+                 b = 1 and v_out = v_c exactly.
+     outputs     device_variance_out[p] = v_out ([H][W] doubles); history_out
+                 var = fp32(v_out), stored as 0 wherever the count is stored
+                 as 0.
+   The contracts and refusals are rt_temporal_device's with the histories'
+   size rt_history_variance_bytes in the alignment and overlap checks, and:
+   device_variance_now is only read; a null device_variance_now or
+   device_variance_out; a device_variance_out that overlaps either history,
+   device_variance_now (every lane reads only its own entry, but in place is
+   refused all the same) or device_out. */
+int rt_temporal_variance_device(const rt_frame *frame_now, const double *device_rgb, double rgb_scale,
+                                const int32_t *device_tile_strata, int32_t strata_now,
+                                const double *device_guides, int32_t guide_strata,
+                                const rt_frame *frame_prev, const void *device_history_prev,
+                                const double *device_variance_now, const rt_temporal_params *params,
+                                void *device_history_out, double *device_out, double *device_variance_out,
+                                void *hip_stream);
+
+/* rt_denoise_variance_device without its estimation stage: v is
+   device_variance[p] ([H][W] doubles, only read; a NaN or negative value is 0)
+   and 0 where e is not finite; the passes, the remodulation, the outputs and
+   the workspace (rt_denoise_variance_workspace_bytes) are that function's.
+   params->min_batches is ignored.  Fed with the plane
+   rt_denoise_variance_device writes at passes < 0 it gives that function's
+   result bit for bit.  RT_ERR_INVALID before anything is queued: everything
+   rt_denoise_variance_device refuses of the arguments both take; a null
+   device_variance; a device_variance that overlaps the workspace, device_out
+   or device_variance_out. */
+int rt_denoise_given_variance_device(const rt_frame *frame, const double *device_rgb, double rgb_scale,
+                                     const int32_t *device_tile_strata, const double *device_guides,
+                                     int32_t guide_strata, const double *device_variance,
+                                     const rt_denoise_variance_params *params, void *device_workspace,
+                                     double *device_out, double *device_variance_out, void *hip_stream);
+
 /* ---- tile exchange (multi-GPU tile sharding) ------------------------------ */
 /* Tile-layout chunk partials [tile][chunk][64][3] (rt_render_device with
    RT_LAYOUT_TILES and strata_chunks = chunks) -> per-tile sums [tile][64][3],

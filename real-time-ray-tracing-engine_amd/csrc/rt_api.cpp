@@ -1072,13 +1072,12 @@ int rt_history_bytes(const rt_frame *f, int64_t *bytes) {
   return RT_OK;
 }
 
-int rt_temporal_device(const rt_frame *f, const double *device_rgb, double rgb_scale,
-                       const int32_t *device_tile_strata, int32_t strata_now, const double *device_guides,
-                       int32_t guide_strata, const rt_frame *frame_prev, const void *device_history_prev,
-                       const rt_temporal_params *params, void *device_history_out, double *device_out,
-                       void *hip_stream) {
-  int64_t tiles = 0;
-  if (int rc = frame_tiles(f, tiles)) return rc;
+// what rt_temporal_device and rt_temporal_variance_device refuse alike; hb: the bytes of one history
+static int temporal_args(const rt_frame *f, const double *device_rgb, const int32_t *device_tile_strata,
+                         int32_t strata_now, const double *device_guides, int32_t guide_strata,
+                         const rt_frame *frame_prev, const void *device_history_prev,
+                         const rt_temporal_params *params, void *device_history_out, double *device_out, size_t hb,
+                         rt_temporal_params &q) {
   if (!device_rgb || !device_guides || !device_history_out || !device_out)
     return set_err(RT_ERR_INVALID, "null argument");
   if (guide_strata < 1) return set_err(RT_ERR_INVALID, "guide_strata must be >= 1");
@@ -1090,7 +1089,6 @@ int rt_temporal_device(const rt_frame *f, const double *device_rgb, double rgb_s
   if (((uintptr_t)device_history_out & 255) != 0 || ((uintptr_t)device_history_prev & 255) != 0)
     return set_err(RT_ERR_INVALID, "a history must be 256-B aligned");
   {
-    const size_t hb = rtk_history_bytes(f->image_width, f->image_height);
     const uintptr_t a0 = (uintptr_t)device_history_out, a1 = a0 + hb;
     const uintptr_t b0 = (uintptr_t)device_history_prev, b1 = b0 + hb;
     const uintptr_t o0 = (uintptr_t)device_out;
@@ -1100,16 +1098,121 @@ int rt_temporal_device(const rt_frame *f, const double *device_rgb, double rgb_s
     if ((o0 < a1 && a0 < o1) || (device_history_prev && o0 < b1 && b0 < o1))
       return set_err(RT_ERR_INVALID, "device_out overlaps a history");
   }
-  rt_temporal_params q{};
+  q = rt_temporal_params{};
   if (params) q = *params;
   if (q.max_history < 0) return set_err(RT_ERR_INVALID, "max_history must be >= 0");
   const double par[3] = {q.sigma_depth, q.sigma_normal, q.hit_min};
   for (double v : par)
     if (v != v) return set_err(RT_ERR_INVALID, "a temporal parameter is NaN");
+  return RT_OK;
+}
+
+int rt_temporal_device(const rt_frame *f, const double *device_rgb, double rgb_scale,
+                       const int32_t *device_tile_strata, int32_t strata_now, const double *device_guides,
+                       int32_t guide_strata, const rt_frame *frame_prev, const void *device_history_prev,
+                       const rt_temporal_params *params, void *device_history_out, double *device_out,
+                       void *hip_stream) {
+  int64_t tiles = 0;
+  if (int rc = frame_tiles(f, tiles)) return rc;
+  rt_temporal_params q{};
+  if (int rc = temporal_args(f, device_rgb, device_tile_strata, strata_now, device_guides, guide_strata, frame_prev,
+                             device_history_prev, params, device_history_out, device_out,
+                             rtk_history_bytes(f->image_width, f->image_height), q))
+    return rc;
   hipError_t e = rtk_launch_temporal(f, device_rgb, rgb_scale, device_tile_strata, strata_now, device_guides,
                                      guide_strata, frame_prev, device_history_prev, &q, device_history_out,
                                      device_out, (hipStream_t)hip_stream);
   if (e != hipSuccess) return hip_err(e, "temporal launch");
+  return RT_OK;
+}
+
+// ---------------------------------------------------------------- temporal variance
+int rt_history_variance_bytes(const rt_frame *f, int64_t *bytes) {
+  int64_t tiles = 0;
+  if (int rc = frame_tiles(f, tiles)) return rc;
+  if (!bytes) return set_err(RT_ERR_INVALID, "null argument");
+  *bytes = (int64_t)rtk_history_variance_bytes(f->image_width, f->image_height);
+  return RT_OK;
+}
+
+int rt_temporal_variance_device(const rt_frame *f, const double *device_rgb, double rgb_scale,
+                                const int32_t *device_tile_strata, int32_t strata_now, const double *device_guides,
+                                int32_t guide_strata, const rt_frame *frame_prev, const void *device_history_prev,
+                                const double *device_variance_now, const rt_temporal_params *params,
+                                void *device_history_out, double *device_out, double *device_variance_out,
+                                void *hip_stream) {
+  int64_t tiles = 0;
+  if (int rc = frame_tiles(f, tiles)) return rc;
+  if (!device_variance_now || !device_variance_out) return set_err(RT_ERR_INVALID, "null argument");
+  const size_t hb = rtk_history_variance_bytes(f->image_width, f->image_height);
+  rt_temporal_params q{};
+  if (int rc = temporal_args(f, device_rgb, device_tile_strata, strata_now, device_guides, guide_strata, frame_prev,
+                             device_history_prev, params, device_history_out, device_out, hb, q))
+    return rc;
+  {
+    const size_t px = (size_t)f->image_width * f->image_height;
+    const uintptr_t a0 = (uintptr_t)device_history_out, a1 = a0 + hb;
+    const uintptr_t b0 = (uintptr_t)device_history_prev, b1 = b0 + hb;
+    const uintptr_t o0 = (uintptr_t)device_out, o1 = o0 + px * 3 * sizeof(double);
+    const uintptr_t n0 = (uintptr_t)device_variance_now, n1 = n0 + px * sizeof(double);
+    const uintptr_t v0 = (uintptr_t)device_variance_out, v1 = v0 + px * sizeof(double);
+    if ((v0 < a1 && a0 < v1) || (device_history_prev && v0 < b1 && b0 < v1))
+      return set_err(RT_ERR_INVALID, "device_variance_out overlaps a history");
+    if (v0 < n1 && n0 < v1) return set_err(RT_ERR_INVALID, "device_variance_out overlaps device_variance_now");
+    if (v0 < o1 && o0 < v1) return set_err(RT_ERR_INVALID, "device_variance_out overlaps device_out");
+  }
+  hipError_t e = rtk_launch_temporal_variance(f, device_rgb, rgb_scale, device_tile_strata, strata_now,
+                                              device_guides, guide_strata, frame_prev, device_history_prev,
+                                              device_variance_now, &q, device_history_out, device_out,
+                                              device_variance_out, (hipStream_t)hip_stream);
+  if (e != hipSuccess) return hip_err(e, "temporal variance launch");
+  return RT_OK;
+}
+
+int rt_denoise_given_variance_device(const rt_frame *f, const double *device_rgb, double rgb_scale,
+                                     const int32_t *device_tile_strata, const double *device_guides,
+                                     int32_t guide_strata, const double *device_variance,
+                                     const rt_denoise_variance_params *params, void *device_workspace,
+                                     double *device_out, double *device_variance_out, void *hip_stream) {
+  int64_t tiles = 0;
+  if (int rc = frame_tiles(f, tiles)) return rc;
+  if (!device_rgb || !device_guides || !device_workspace || !device_out || !device_variance)
+    return set_err(RT_ERR_INVALID, "null argument");
+  if (guide_strata < 1) return set_err(RT_ERR_INVALID, "guide_strata must be >= 1");
+  if (((uintptr_t)device_workspace & 255) != 0) return set_err(RT_ERR_INVALID, "workspace must be 256-B aligned");
+  {
+    const size_t px = (size_t)f->image_width * f->image_height;
+    const uintptr_t w0 = (uintptr_t)device_workspace;
+    const uintptr_t w1 = w0 + rtk_denoise_variance_workspace_bytes(f->image_width, f->image_height);
+    const uintptr_t o0 = (uintptr_t)device_out, o1 = o0 + px * 3 * sizeof(double);
+    const uintptr_t v0 = (uintptr_t)device_variance_out, v1 = v0 + px * sizeof(double);
+    const uintptr_t g0 = (uintptr_t)device_variance, g1 = g0 + px * sizeof(double);
+    if (o0 < w1 && w0 < o1) return set_err(RT_ERR_INVALID, "device_out overlaps the workspace");
+    if (device_variance_out && v0 < w1 && w0 < v1)
+      return set_err(RT_ERR_INVALID, "device_variance_out overlaps the workspace");
+    if (device_variance_out && v0 < o1 && o0 < v1)
+      return set_err(RT_ERR_INVALID, "device_variance_out overlaps device_out");
+    if (g0 < w1 && w0 < g1) return set_err(RT_ERR_INVALID, "device_variance overlaps the workspace");
+    if (g0 < o1 && o0 < g1) return set_err(RT_ERR_INVALID, "device_variance overlaps device_out");
+    if (device_variance_out && g0 < v1 && v0 < g1)
+      return set_err(RT_ERR_INVALID, "device_variance overlaps device_variance_out");
+  }
+  rt_denoise_variance_params q{};
+  if (params) q = *params;
+  if (q.passes > RT_DENOISE_MAX_PASSES)
+    return set_err(RT_ERR_INVALID, "passes must be at most " + std::to_string(RT_DENOISE_MAX_PASSES));
+  const double sig[4] = {q.sigma_normal, q.sigma_depth, q.sigma_hit, q.sigma_lum};
+  for (double v : sig)
+    if (v != v) return set_err(RT_ERR_INVALID, "a sigma is NaN");
+  auto pick = [](double v, double dflt) { return v == 0.0 ? dflt : v; }; // < 0: off
+  const int passes = q.passes == 0 ? RT_DENOISE_PASSES : q.passes;
+  hipError_t e = rtk_launch_denoise_given_variance(
+      f->image_width, f->image_height, device_rgb, rgb_scale, device_tile_strata, device_guides, guide_strata,
+      device_variance, passes, pick(q.sigma_normal, RT_DENOISE_SIGMA_NORMAL),
+      pick(q.sigma_depth, RT_DENOISE_SIGMA_DEPTH), pick(q.sigma_hit, RT_DENOISE_SIGMA_HIT),
+      pick(q.sigma_lum, RT_DENOISE_SIGMA_LUM), device_workspace, device_out, device_variance_out,
+      (hipStream_t)hip_stream);
+  if (e != hipSuccess) return hip_err(e, "given-variance denoise launch");
   return RT_OK;
 }
 

@@ -205,6 +205,39 @@ __global__ void __launch_bounds__(256)
   hit[p] = (float)(hits * inv_g);
 }
 
+// variance_prepare_kernel with v given by the caller (rt_denoise_given_variance_device,
+// DESIGN.md §7g): the moments block is one load; a NaN or negative value is 0,
+// and so is v where e is not finite.  Nothing is left for variance_spatial_kernel.
+__global__ void __launch_bounds__(256)
+    variance_prepare_given_kernel(const double *rgb, double scale, const int32_t *tile_strata, const double *guides,
+                                  double inv_g, const double *variance, int W, int H, int tiles_x, float4 *col,
+                                  float4 *geo, float4 *alb, float *hit) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= (int64_t)W * H) return;
+  double s = scale;
+  if (tile_strata != nullptr) {
+    const int i = (int)(p % W), j = (int)(p / W);
+    s = 1.0 / (double)max(1, tile_strata[(j >> 3) * tiles_x + (i >> 3)]);
+  }
+  const double *G = guides + 8 * p;
+  float e[3];
+  double ad[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const double a = G[c] * inv_g;
+    ad[c] = a > 0.01 ? a : 0.01;
+    e[c] = (float)(rgb[3 * p + c] * s / ad[c]);
+  }
+  const double vp = variance[p];
+  const float v = (vp > 0.0 && finite3(e[0], e[1], e[2])) ? (float)vp : 0.0f;
+  const double hits = G[7];
+  col[p] = make_float4(e[0], e[1], e[2], v);
+  geo[p] = make_float4((float)(G[3] * inv_g), (float)(G[4] * inv_g), (float)(G[5] * inv_g),
+                       (float)(G[6] / (hits > 1.0 ? hits : 1.0)));
+  alb[p] = make_float4((float)ad[0], (float)ad[1], (float)ad[2], 0.0f);
+  hit[p] = (float)(hits * inv_g);
+}
+
 // three floats of a col entry: the spatial kernel reads e while other lanes
 // store their own v beside it, so it never touches the w slot of another pixel
 __device__ __forceinline__ float4 load_e(const float4 *col, int64_t q) {
@@ -357,6 +390,53 @@ extern "C" size_t rtk_denoise_variance_workspace_bytes(int W, int H) {
   return 4 * pad256((size_t)W * H * sizeof(float4)) + pad256((size_t)W * H * sizeof(float));
 }
 
+namespace {
+
+// the workspace's planes
+struct VarianceWs {
+  float4 *col[2], *geo, *alb;
+  float *hit;
+};
+VarianceWs variance_ws(void *workspace, int64_t n) {
+  const size_t plane = pad256((size_t)n * sizeof(float4));
+  char *ws = static_cast<char *>(workspace);
+  return VarianceWs{{reinterpret_cast<float4 *>(ws), reinterpret_cast<float4 *>(ws + plane)},
+                    reinterpret_cast<float4 *>(ws + 2 * plane), reinterpret_cast<float4 *>(ws + 3 * plane),
+                    reinterpret_cast<float *>(ws + 4 * plane)};
+}
+
+PassCoef variance_coef(double sigma_n, double sigma_z, double sigma_h) {
+  PassCoef K;
+  K.inv_sn2 = sigma_n > 0 ? (float)(1.0 / (sigma_n * sigma_n)) : 0.0f;
+  K.inv_sz = sigma_z > 0 ? (float)(1.0 / sigma_z) : 0.0f;
+  K.inv_sh2 = sigma_h > 0 ? (float)(1.0 / (sigma_h * sigma_h)) : 0.0f;
+  K.inv_sc2 = 0.0f;
+  return K;
+}
+
+// the passes (or, passes <= 0, the remodulation alone) over a prepared workspace whose col[0] holds v
+hipError_t variance_passes(const VarianceWs &ws, int W, int H, int passes, PassCoef K, double sigma_l, double *out,
+                           double *var_out, hipStream_t stream) {
+  const int64_t n = (int64_t)W * H;
+  if (passes <= 0) {
+    hipLaunchKernelGGL(variance_remodulate_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
+                       ws.col[0], ws.alb, n, out, var_out);
+    return hipGetLastError();
+  }
+  const dim3 grid((unsigned)((W + kBX - 1) / kBX), (unsigned)((H + kBY - 1) / kBY));
+  for (int k = 0; k < passes; ++k) {
+    const bool last = k == passes - 1;
+    hipLaunchKernelGGL(variance_pass_kernel, grid, dim3(kBX * kBY), 0, stream, ws.col[k & 1], ws.geo, ws.hit, ws.alb,
+                       W, H, 1 << k, K, sigma_l > 0 ? (float)sigma_l : 0.0f, ws.col[(k & 1) ^ 1],
+                       last ? out : nullptr, last ? var_out : nullptr);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+} // namespace
+
 extern "C" hipError_t rtk_launch_denoise_variance(int W, int H, const double *rgb, double scale,
                                                   const int32_t *tile_strata, const double *guides,
                                                   int guide_strata, const double *s1, const double *s2,
@@ -365,12 +445,7 @@ extern "C" hipError_t rtk_launch_denoise_variance(int W, int H, const double *rg
                                                   double *out, double *var_out, hipStream_t stream) {
   const int64_t n = (int64_t)W * H;
   if (n <= 0) return hipSuccess;
-  const size_t plane = pad256((size_t)n * sizeof(float4));
-  char *ws = static_cast<char *>(workspace);
-  float4 *col[2] = {reinterpret_cast<float4 *>(ws), reinterpret_cast<float4 *>(ws + plane)};
-  float4 *geo = reinterpret_cast<float4 *>(ws + 2 * plane);
-  float4 *alb = reinterpret_cast<float4 *>(ws + 3 * plane);
-  float *hit = reinterpret_cast<float *>(ws + 4 * plane);
+  const VarianceWs ws = variance_ws(workspace, n);
   const int tiles_x = (W + 7) / 8;
   if (!(s1 && s2 && tile_strata && batch_strata >= 1)) { // no moments: every pixel takes the spatial estimate
     s1 = s2 = nullptr;
@@ -378,34 +453,35 @@ extern "C" hipError_t rtk_launch_denoise_variance(int W, int H, const double *rg
   }
   const unsigned blocks = (unsigned)((n + 255) / 256);
   hipLaunchKernelGGL(variance_prepare_kernel, dim3(blocks), dim3(256), 0, stream, rgb, scale, tile_strata, guides,
-                     1.0 / (double)guide_strata, s1, s2, batch_strata, min_batches, W, H, tiles_x, col[0], geo, alb,
-                     hit);
+                     1.0 / (double)guide_strata, s1, s2, batch_strata, min_batches, W, H, tiles_x, ws.col[0], ws.geo,
+                     ws.alb, ws.hit);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  PassCoef K;
-  K.inv_sn2 = sigma_n > 0 ? (float)(1.0 / (sigma_n * sigma_n)) : 0.0f;
-  K.inv_sz = sigma_z > 0 ? (float)(1.0 / sigma_z) : 0.0f;
-  K.inv_sh2 = sigma_h > 0 ? (float)(1.0 / (sigma_h * sigma_h)) : 0.0f;
-  K.inv_sc2 = 0.0f;
+  const PassCoef K = variance_coef(sigma_n, sigma_z, sigma_h);
   const dim3 grid((unsigned)((W + kBX - 1) / kBX), (unsigned)((H + kBY - 1) / kBY));
-  hipLaunchKernelGGL(variance_spatial_kernel, grid, dim3(kBX * kBY), 0, stream, col[0], geo, hit, tile_strata,
-                     batch_strata, min_batches, W, H, tiles_x, K);
+  hipLaunchKernelGGL(variance_spatial_kernel, grid, dim3(kBX * kBY), 0, stream, ws.col[0], ws.geo, ws.hit,
+                     tile_strata, batch_strata, min_batches, W, H, tiles_x, K);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
-  if (passes <= 0) {
-    hipLaunchKernelGGL(variance_remodulate_kernel, dim3(blocks), dim3(256), 0, stream, col[0], alb, n, out,
-                       var_out);
-    return hipGetLastError();
-  }
-  for (int k = 0; k < passes; ++k) {
-    const bool last = k == passes - 1;
-    hipLaunchKernelGGL(variance_pass_kernel, grid, dim3(kBX * kBY), 0, stream, col[k & 1], geo, hit, alb, W, H,
-                       1 << k, K, sigma_l > 0 ? (float)sigma_l : 0.0f, col[(k & 1) ^ 1], last ? out : nullptr,
-                       last ? var_out : nullptr);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  return variance_passes(ws, W, H, passes, K, sigma_l, out, var_out, stream);
+}
+
+// the same passes on a variance plane the caller gives: no estimation stage
+extern "C" hipError_t rtk_launch_denoise_given_variance(int W, int H, const double *rgb, double scale,
+                                                        const int32_t *tile_strata, const double *guides,
+                                                        int guide_strata, const double *variance, int passes,
+                                                        double sigma_n, double sigma_z, double sigma_h,
+                                                        double sigma_l, void *workspace, double *out,
+                                                        double *var_out, hipStream_t stream) {
+  const int64_t n = (int64_t)W * H;
+  if (n <= 0) return hipSuccess;
+  const VarianceWs ws = variance_ws(workspace, n);
+  hipLaunchKernelGGL(variance_prepare_given_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, rgb,
+                     scale, tile_strata, guides, 1.0 / (double)guide_strata, variance, W, H, (W + 7) / 8, ws.col[0],
+                     ws.geo, ws.alb, ws.hit);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  return variance_passes(ws, W, H, passes, variance_coef(sigma_n, sigma_z, sigma_h), sigma_l, out, var_out, stream);
 }
 
 extern "C" size_t rtk_denoise_workspace_bytes(int W, int H) {

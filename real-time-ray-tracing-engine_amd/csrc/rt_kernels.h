@@ -69,8 +69,21 @@ hipError_t rtk_launch_denoise_variance(int W, int H, const double *rgb, double s
                                        double sigma_z, double sigma_h, double sigma_l, void *workspace,
                                        double *out, double *var_out, hipStream_t stream);
 
+// the same passes on the caller's variance plane ([H][W] double): no estimation stage
+hipError_t rtk_launch_denoise_given_variance(int W, int H, const double *rgb, double scale,
+                                             const int32_t *tile_strata, const double *guides, int guide_strata,
+                                             const double *variance, int passes, double sigma_n, double sigma_z,
+                                             double sigma_h, double sigma_l, void *workspace, double *out,
+                                             double *var_out, hipStream_t stream);
+
 // ---- rt_temporal.hip: the temporal reprojection (params checked, may be null; prev /
-// history_prev both null: no history)
+// history_prev both null: no history); the _variance pair takes histories with a var plane
+size_t rtk_history_variance_bytes(int W, int H);
+hipError_t rtk_launch_temporal_variance(const rt_frame *now, const double *rgb, double scale,
+                                        const int32_t *tile_strata, int strata_now, const double *guides,
+                                        int guide_strata, const rt_frame *prev, const void *history_prev,
+                                        const double *variance_now, const rt_temporal_params *params,
+                                        void *history_out, double *out, double *variance_out, hipStream_t stream);
 size_t rtk_history_bytes(int W, int H);
 hipError_t rtk_launch_temporal(const rt_frame *now, const double *rgb, double scale, const int32_t *tile_strata,
                                int strata_now, const double *guides, int guide_strata, const rt_frame *prev,

@@ -8,7 +8,9 @@
 // two fp32 float4 planes: col (e.r, e.g, e.b, count) and geo (n.x, n.y, n.z, z).
 // A pixel reads its own rgb / guides and at most four taps of the previous
 // planes (two 16-B loads each) and writes its own col, geo and out once: no
-// atomics, no shared memory, nothing read that another pixel writes.
+// atomics, no shared memory, nothing read that another pixel writes.  A
+// variance history (rt_temporal_variance_device) adds a third plane, var: the
+// fp32 variance of e's luminance, one 4-B load per tap and one store.
 #ifndef RT_TEMPORAL_H
 #define RT_TEMPORAL_H
 #include <math.h>
@@ -85,12 +87,20 @@ RT_HD RT_FI D3 centre_point(const Cam &C, int i, int j, double z) {
 
 RT_HD RT_FI bool finite1(double x) { return fabs(x) < __builtin_huge_val(); }
 
-// One pixel (i, j) of a W x H frame.  pcol / pgeo: the previous history's
-// planes, both null when there is none.  out may be rgb.
-RT_HD RT_FI void temporal_pixel(const Cam &now, const Cam &prev, int W, int H, int i, int j, const double *rgb,
-                                  double scale, const int32_t *tile_strata, int strata_now,
-                                  const double *guides, double g, const F4 *pcol, const F4 *pgeo,
-                                  const Coef &K, F4 *ocol, F4 *ogeo, double *out) {
+// One pixel (i, j) of a W x H frame: the projection, the tap loop and the blend,
+// stated once for temporal_pixel and temporal_variance_pixel.  pcol / pgeo: the
+// previous history's planes, both null when there is none.  out may be rgb.
+// VAR (rt_temporal_variance_device; rtx/temporal.py NumpyOps.temporal_variance,
+// DESIGN.md §7g) carries the luminance variance of e beside the colour: pvar /
+// ovar are the histories' third planes (fp32 scalars; pvar null with pcol),
+// v_now / v_out [H][W] double planes.  Without VAR none of them is touched and
+// the colour arithmetic is the same operations in the same order.
+template <bool VAR>
+RT_HD RT_FI void temporal_core(const Cam &now, const Cam &prev, int W, int H, int i, int j, const double *rgb,
+                                 double scale, const int32_t *tile_strata, int strata_now,
+                                 const double *guides, double g, const F4 *pcol, const F4 *pgeo,
+                                 const float *pvar, const Coef &K, F4 *ocol, F4 *ogeo, double *out,
+                                 const double *v_now, float *ovar, double *v_out) {
   const int64_t p = (int64_t)j * W + i;
   double s = scale, n_c = (double)strata_now;
   if (tile_strata != nullptr) { // rt_to_bytes_tiles_device's scale; the tile's own count
@@ -110,7 +120,7 @@ RT_HD RT_FI void temporal_pixel(const Cam &now, const Cam &prev, int W, int H, i
   const D3 n = D3{G[3] / g, G[4] / g, G[5] / g};
   const double z = G[6] / (hits > 1.0 ? hits : 1.0);
 
-  double n_h = 0.0, eh[3] = {0.0, 0.0, 0.0};
+  double n_h = 0.0, eh[3] = {0.0, 0.0, 0.0}, v_h = 0.0;
   if (pcol != nullptr && h >= K.hit_min) {
     const D3 P = centre_point(now, i, j, z);
     const D3 v = P - prev.c;
@@ -129,7 +139,7 @@ RT_HD RT_FI void temporal_pixel(const Cam &now, const Cam &prev, int W, int H, i
         const double nn = dot(n, n);
         const bool plane = nn >= 0.25;
         const D3 nu = plane ? (1.0 / sqrt(nn)) * n : n;
-        double Wv = 0.0, cnt = 0.0, se[3] = {0.0, 0.0, 0.0};
+        double Wv = 0.0, cnt = 0.0, se[3] = {0.0, 0.0, 0.0}, sv = 0.0;
         for (int b = 0; b < 2; ++b) {
           const int qy = y0 + b;
           if (qy < 0 || qy >= H) continue;
@@ -160,12 +170,18 @@ RT_HD RT_FI void temporal_pixel(const Cam &now, const Cam &prev, int W, int H, i
               se[0] += w * (double)cq.x;
               se[1] += w * (double)cq.y;
               se[2] += w * (double)cq.z;
+              if (VAR) { // linear, not w^2: neighbouring history pixels share taps
+                const float vq = pvar[t];
+                // a NaN or negative v': 0; a tap of weight 0 adds nothing (0 inf is not a variance)
+                if (w > 0.0) sv += w * (double)(vq > 0.0f ? vq : 0.0f);
+              }
             }
           }
         }
         if (Wv > 0.0) {
           n_h = cnt < K.max_history ? cnt : K.max_history;
           for (int c = 0; c < 3; ++c) eh[c] = se[c] / Wv;
+          if (VAR) v_h = sv / Wv; // the cap bounds the count, not the variance
         }
       }
     }
@@ -182,6 +198,37 @@ RT_HD RT_FI void temporal_pixel(const Cam &now, const Cam &prev, int W, int H, i
   const double count = (h >= K.hit_min && fin) ? total : 0.0;
   ocol[p] = F4{(float)eo[0], (float)eo[1], (float)eo[2], (float)count};
   ogeo[p] = F4{(float)n.x, (float)n.y, (float)n.z, (float)z};
+  if (VAR) {
+    const double vn = v_now[p];
+    const double v_c = vn > 0.0 ? vn : 0.0; // a NaN or negative variance: 0
+    double vo = 0.0;
+    if (total > 0.0) { // a term whose count is 0 is dropped, not multiplied (0 inf)
+      const double a = n_h / total, b = n_c / total;
+      if (n_h > 0.0) vo = (a * a) * v_h;
+      if (n_c > 0.0) vo = vo + (b * b) * v_c; // no history: b = 1, v_c itself
+    }
+    v_out[p] = vo;
+    ovar[p] = count > 0.0 ? (float)vo : 0.0f;
+  }
+}
+
+RT_HD RT_FI void temporal_pixel(const Cam &now, const Cam &prev, int W, int H, int i, int j, const double *rgb,
+                                  double scale, const int32_t *tile_strata, int strata_now,
+                                  const double *guides, double g, const F4 *pcol, const F4 *pgeo,
+                                  const Coef &K, F4 *ocol, F4 *ogeo, double *out) {
+  temporal_core<false>(now, prev, W, H, i, j, rgb, scale, tile_strata, strata_now, guides, g, pcol, pgeo, nullptr, K,
+                       ocol, ogeo, out, nullptr, nullptr, nullptr);
+}
+
+// temporal_pixel with the variance carried along: every colour output is
+// temporal_pixel's, bit for bit.  v_out may not be v_now.
+RT_HD RT_FI void temporal_variance_pixel(const Cam &now, const Cam &prev, int W, int H, int i, int j,
+                                           const double *rgb, double scale, const int32_t *tile_strata,
+                                           int strata_now, const double *guides, double g, const F4 *pcol,
+                                           const F4 *pgeo, const float *pvar, const Coef &K, F4 *ocol, F4 *ogeo,
+                                           float *ovar, double *out, const double *v_now, double *v_out) {
+  temporal_core<true>(now, prev, W, H, i, j, rgb, scale, tile_strata, strata_now, guides, g, pcol, pgeo, pvar, K,
+                      ocol, ogeo, out, v_now, ovar, v_out);
 }
 
 } // namespace rtt

@@ -8,6 +8,8 @@
 // taps land on row segments of the previous planes shifted by the camera
 // move -- near-contiguous 16-B-per-lane loads.  No atomics, no LDS; every pixel
 // writes its own outputs once, so two runs are bit-identical.
+// rt_temporal_variance_device is a second kernel of the same shape over a
+// history with a third plane (the variance of e's luminance).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -30,11 +32,58 @@ __global__ void __launch_bounds__(kBX *kBY)
                       ocol, ogeo, out);
 }
 
+// temporal_kernel with the variance of e's luminance carried along
+// (rt_temporal_variance_device): the same lane-per-pixel shape;
+// over temporal_kernel's traffic a lane reads its own 8-B variance_now and one
+// 4-B var per tap (the taps' row segments again) and writes 8 B variance_out
+// and 4 B var -- contiguous per wavefront.
+__global__ void __launch_bounds__(kBX *kBY)
+    temporal_variance_kernel(rtt::Cam now, rtt::Cam prev, int W, int H, const double *rgb, double scale,
+                             const int32_t *tile_strata, int strata_now, const double *guides, double g,
+                             const rtt::F4 *pcol, const rtt::F4 *pgeo, const float *pvar, rtt::Coef K,
+                             rtt::F4 *ocol, rtt::F4 *ogeo, float *ovar, double *out, const double *v_now,
+                             double *v_out) {
+  const int x = blockIdx.x * kBX + (threadIdx.x & (kBX - 1));
+  const int y = blockIdx.y * kBY + (threadIdx.x / kBX);
+  if (x >= W || y >= H) return;
+  rtt::temporal_variance_pixel(now, prev, W, H, x, y, rgb, scale, tile_strata, strata_now, guides, g, pcol, pgeo,
+                               pvar, K, ocol, ogeo, ovar, out, v_now, v_out);
+}
+
 } // namespace
 
 extern "C" size_t rtk_history_bytes(int W, int H) {
   const size_t plane = (((size_t)W * H * sizeof(rtt::F4)) + 255) & ~(size_t)255;
   return 2 * plane;
+}
+
+// a plain history and the var plane (fp32 scalars) behind it
+extern "C" size_t rtk_history_variance_bytes(int W, int H) {
+  return rtk_history_bytes(W, H) + ((((size_t)W * H * sizeof(float)) + 255) & ~(size_t)255);
+}
+
+extern "C" hipError_t rtk_launch_temporal_variance(const rt_frame *now, const double *rgb, double scale,
+                                                   const int32_t *tile_strata, int strata_now,
+                                                   const double *guides, int guide_strata, const rt_frame *prev,
+                                                   const void *history_prev, const double *variance_now,
+                                                   const rt_temporal_params *params, void *history_out,
+                                                   double *out, double *variance_out, hipStream_t stream) {
+  const int W = now->image_width, H = now->image_height;
+  if ((int64_t)W * H <= 0) return hipSuccess;
+  const size_t plane = rtk_history_bytes(W, H) / 2;
+  const rtt::Coef K = rtt::coef_of(params);
+  const char *hp = static_cast<const char *>(history_prev);
+  char *ho = static_cast<char *>(history_out);
+  const rtt::F4 *pcol = reinterpret_cast<const rtt::F4 *>(hp);
+  const rtt::F4 *pgeo = hp ? reinterpret_cast<const rtt::F4 *>(hp + plane) : nullptr;
+  const float *pvar = hp ? reinterpret_cast<const float *>(hp + 2 * plane) : nullptr;
+  const rtt::Cam cn = rtt::cam_of(*now), cp = rtt::cam_of(prev ? *prev : *now);
+  const dim3 grid((unsigned)((W + kBX - 1) / kBX), (unsigned)((H + kBY - 1) / kBY));
+  hipLaunchKernelGGL(temporal_variance_kernel, grid, dim3(kBX * kBY), 0, stream, cn, cp, W, H, rgb, scale,
+                     tile_strata, strata_now, guides, (double)guide_strata, pcol, pgeo, pvar, K,
+                     reinterpret_cast<rtt::F4 *>(ho), reinterpret_cast<rtt::F4 *>(ho + plane),
+                     reinterpret_cast<float *>(ho + 2 * plane), out, variance_now, variance_out);
+  return hipGetLastError();
 }
 
 extern "C" hipError_t rtk_launch_temporal(const rt_frame *now, const double *rgb, double scale,

@@ -249,4 +249,5 @@ EXPORTS = (
     "rt_render_guides_device", "rt_denoise_workspace_bytes", "rt_denoise_device",
     "rt_history_bytes", "rt_temporal_device",
     "rt_denoise_variance_workspace_bytes", "rt_denoise_variance_device",
+    "rt_history_variance_bytes", "rt_temporal_variance_device", "rt_denoise_given_variance_device",
 )

@@ -61,6 +61,12 @@ over the in-image pixels with a finite e, renormalised (not halved per pass:
 v itself shrinks).  The variance is filtered with the colour:
 v'_p = sum w^2 v_q / (sum w)^2, or v_p when sum w = 0.  out = e a_d, and
 optionally the final v.
+
+The same filter on a variance the caller gives (rt_denoise_given_variance_device,
+NumpyOps.denoise_given_variance): no estimation stage -- v is the given plane
+(a NaN or negative entry: 0), 0 where e is not finite -- and the same passes.
+rtx.temporal.TemporalVarianceDisplay feeds it the variance its blend carries
+across camera moves.
 """
 import ctypes as C
 
@@ -309,6 +315,25 @@ class NumpyOps:
             e, v = self.one_pass(e, n, z, h, k, sn, sz, sh, None, v, sl)
         return (e * a_d, v) if with_variance else e * a_d
 
+    def denoise_given_variance(self, frame, rgb, scale, tile_strata, guides, guide_strata, variance, params=None,
+                               with_variance=False):
+        """rt_denoise_given_variance_device: denoise_variance without its
+        estimation stage.  v is `variance` ([H, W]; a NaN or negative entry is
+        0), and 0 where e is not finite; min_batches is ignored."""
+        if guide_strata < 1:
+            raise ValueError("guide_strata must be >= 1")
+        passes, _, sn, sz, sh, sl = resolve_variance(params)
+        e, a_d, n, z, h = self.prepare(frame, rgb, scale, tile_strata, guides, guide_strata)
+        v = np.asarray(variance, dtype=np.float64)
+        if v.shape != e.shape[:2]:
+            raise ValueError("variance must be [H, W]")
+        with np.errstate(invalid="ignore"):
+            v = np.where(v > 0.0, v, 0.0)
+        v = np.where(np.isfinite(e).all(-1), v, 0.0)
+        for k in range(passes):
+            e, v = self.one_pass(e, n, z, h, k, sn, sz, sh, None, v, sl)
+        return (e * a_d, v) if with_variance else e * a_d
+
     def bytes(self, image):
         return to_bytes(image)
 
@@ -381,6 +406,26 @@ class HipOps:
             C.byref(frame), ptr(rgb), C.c_double(scale), ptr(tile_strata), ptr(guides), int(guide_strata),
             ptr(s1), ptr(s2), int(batch_strata), C.byref(p) if p is not None else None, ptr(workspace), ptr(out),
             ptr(variance_out), self._sp()))
+        return out
+
+    def denoise_given_variance(self, frame, rgb, scale, tile_strata, guides, guide_strata, variance, params=None,
+                               workspace=None, out=None, variance_out=None):
+        """rt_denoise_given_variance_device: the passes on the caller's `variance` plane ([H, W] float64)."""
+        t = self.torch
+        if workspace is None:
+            workspace = self.variance_workspace(frame)
+        if out is None:
+            with t.cuda.stream(self.stream):
+                out = t.empty((frame.image_height, frame.image_width, 3), dtype=t.float64, device=self.device)
+
+        def ptr(a):
+            return C.c_void_p(a.data_ptr() if a is not None else 0)
+
+        p = abi.denoise_variance_params(params)
+        check(self.lib.rt_denoise_given_variance_device(
+            C.byref(frame), ptr(rgb), C.c_double(scale), ptr(tile_strata), ptr(guides), int(guide_strata),
+            ptr(variance), C.byref(p) if p is not None else None, ptr(workspace), ptr(out), ptr(variance_out),
+            self._sp()))
         return out
 
     def bytes(self, image, out=None):

@@ -84,6 +84,14 @@ def load():
                                              C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
                                              P(abi.DenoiseVarianceParams), C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_void_p]
+    L.rt_history_variance_bytes.argtypes = [P(abi.Frame), P(C.c_int64)]
+    L.rt_temporal_variance_device.argtypes = [P(abi.Frame), C.c_void_p, C.c_double, C.c_void_p, C.c_int32,
+                                              C.c_void_p, C.c_int32, P(abi.Frame), C.c_void_p, C.c_void_p,
+                                              P(abi.TemporalParams), C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p]
+    L.rt_denoise_given_variance_device.argtypes = [P(abi.Frame), C.c_void_p, C.c_double, C.c_void_p, C.c_void_p,
+                                                   C.c_int32, C.c_void_p, P(abi.DenoiseVarianceParams),
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     for name in abi.EXPORTS:
         getattr(L, name).restype = C.c_char_p if name == "rt_last_error" else C.c_int
     if L.rt_abi_version() != abi.RT_ABI_VERSION:

@@ -52,6 +52,28 @@ the current accumulator, so nothing compounds from frame to frame.  On a move
 the host swaps: the last displayed frame's history_out becomes history_prev
 (TemporalDisplay.reset).
 
+Temporal variance (NumpyOps.temporal_variance, rt_temporal_variance_device;
+TemporalVarianceDisplay).  TemporalDisplay's filter knows nothing of how
+converged the blend is, and VarianceGuidedDisplay forgets it on a move.  A
+variance history has a third plane, var (fp32 [H, W], padded to 256 B, behind
+col and geo: its first history_bytes are a plain history): the variance v of
+the Rec. 709 luminance of e, rtx.denoise's unit.  Everything above is unchanged,
+bit for bit; added per pixel:
+
+ 7. v_c = variance_now[p], 0 when that is NaN or negative.  With Wv > 0,
+    v_h = sum w max(v'_q, 0) / Wv over the valid taps (a NaN v'_q is 0; a tap
+    of weight 0 adds nothing, an infinite one included).  Linear in w, not
+    sum w^2 v' / Wv^2: after one reprojection neighbouring history pixels
+    share taps and are correlated, crediting the interpolation with a variance
+    reduction would compound over moves, and an overestimate only keeps the
+    filter wider.  max_history caps n_h and leaves v_h alone.
+ 8. with a = n_h / total, b = n_c / total: v_out = a^2 v_h + b^2 v_c, a term
+    whose count is 0 dropped (not multiplied), 0 when total = 0; without
+    history b = 1 and v_out = v_c exactly.  variance_out = v_out (float64);
+    history var = fp32(v_out), 0 wherever the count is stored as 0.
+
+rtx.denoise's denoise_given_variance then filters the blend with v_out.
+
 Out of scope: moving spheres get no motion vectors (their blur is already in
 every frame's time average), and reflections and refractions are reprojected
 at their first-hit point; max_history bounds how long either can lag.
@@ -61,7 +83,7 @@ import ctypes as C
 import numpy as np
 
 from . import abi
-from .denoise import DenoisedDisplay
+from .denoise import DenoisedDisplay, VarianceGuidedDisplay
 from .denoise import NumpyOps as _FilterOps
 from .lib import check, load
 
@@ -106,6 +128,29 @@ def unpack_history(frame, buf):
     return tuple(buf[k * half:k * half + h * w * 16].view(np.float32).reshape(h, w, 4).copy() for k in range(2))
 
 
+def history_variance_bytes(frame):
+    """rt_history_variance_bytes: a history and the var plane (fp32 scalars, padded to 256 B) behind it."""
+    return history_bytes(frame) + ((frame.image_width * frame.image_height * 4 + 255) & ~255)
+
+
+def pack_variance_history(frame, history):
+    """(col, geo, var) -> the device layout, a uint8 array of history_variance_bytes."""
+    n = frame.image_width * frame.image_height * 4
+    hb = history_bytes(frame)
+    buf = np.zeros(history_variance_bytes(frame), dtype=np.uint8)
+    buf[:hb] = pack_history(frame, history[:2])
+    buf[hb:hb + n] = np.ascontiguousarray(history[2], dtype=np.float32).reshape(-1).view(np.uint8)
+    return buf
+
+
+def unpack_variance_history(frame, buf):
+    """The device layout -> (col, geo, var): float32 [H, W, 4] twice and [H, W]."""
+    h, w = frame.image_height, frame.image_width
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    hb = history_bytes(frame)
+    return unpack_history(frame, buf[:hb]) + (buf[hb:hb + h * w * 4].view(np.float32).reshape(h, w).copy(),)
+
+
 def _cam(frame):
     def v(a):
         return np.array([a.x, a.y, a.z], dtype=np.float64)
@@ -136,6 +181,9 @@ class NumpyOps:
     def history_bytes(self, frame):
         return history_bytes(frame)
 
+    def history_variance_bytes(self, frame):
+        return history_variance_bytes(frame)
+
     def temporal(self, frame_now, rgb, scale, tile_strata, strata_now, guides, guide_strata, frame_prev=None,
                  history_prev=None, params=None):
         """-> (out [H, W, 3] float64, (col, geo) float32 [H, W, 4] each, margin [H, W]).
@@ -144,6 +192,20 @@ class NumpyOps:
         comparisons of the pixel's taps with w > 1e-6 (inf where it has none):
         a pixel with a tiny margin sits on a threshold, where another rounding
         of the same arithmetic may decide the other way."""
+        return self._temporal(frame_now, rgb, scale, tile_strata, strata_now, guides, guide_strata, frame_prev,
+                              history_prev, params, None)
+
+    def temporal_variance(self, frame_now, rgb, scale, tile_strata, strata_now, guides, guide_strata, variance_now,
+                          frame_prev=None, history_prev=None, params=None):
+        """rt_temporal_variance_device -> (out, (col, geo, var), variance_out
+        [H, W] float64, margin); history_prev is a (col, geo, var) triple, var
+        float32 [H, W].  out, col, geo and margin are temporal()'s."""
+        return self._temporal(frame_now, rgb, scale, tile_strata, strata_now, guides, guide_strata, frame_prev,
+                              history_prev, params, variance_now)
+
+    def _temporal(self, frame_now, rgb, scale, tile_strata, strata_now, guides, guide_strata, frame_prev,
+                  history_prev, params, variance_now):
+        """temporal() and, with variance_now, temporal_variance(): the colour is stated once."""
         if guide_strata < 1:
             raise ValueError("guide_strata must be >= 1")
         if (frame_prev is None) != (history_prev is None):
@@ -153,10 +215,19 @@ class NumpyOps:
         e, a_d, n, z, h = _FilterOps().prepare(frame_now, rgb, scale, tile_strata, guides, guide_strata)
         n_c = _pixel_tiles(tile_strata, frame_now) if tile_strata is not None else np.full((H, W), float(strata_now))
         n_h, e_h, margin = np.zeros((H, W)), np.zeros((H, W, 3)), np.full((H, W), np.inf)
+        with_var = variance_now is not None
+        v_h = np.zeros((H, W))
         if history_prev is not None:
             if (frame_prev.image_width, frame_prev.image_height) != (W, H):
                 raise ValueError("frame_prev has another size than frame_now")
-            col, geo = (np.asarray(a, dtype=np.float64) for a in history_prev)
+            if len(history_prev) != (3 if with_var else 2):
+                raise ValueError("a variance history is (col, geo, var), a plain one (col, geo)")
+            col, geo = (np.asarray(a, dtype=np.float64) for a in history_prev[:2])
+            if with_var:
+                var = np.asarray(history_prev[2], dtype=np.float64)
+                with np.errstate(invalid="ignore"):
+                    var = np.where(var > 0.0, var, 0.0)  # a NaN or negative v': 0
+            sv = np.zeros((H, W))
             jj, ii = np.mgrid[0:H, 0:W]
             prev = _cam(frame_prev)
             cp, p00p, dup, dvp = prev
@@ -200,9 +271,12 @@ class NumpyOps:
                     Wv += w
                     cnt += w * np.where(ok, cq[..., 3], 0.0)
                     se += w[..., None] * np.where(ok[..., None], cq[..., :3], 0.0)
+                    if with_var:  # linear in w, not w^2: neighbouring history pixels share taps
+                        sv += w * np.where(w > 0, var[cy, cx], 0.0)  # w = 0: nothing, an infinite v' included
             some = Wv > 0
             n_h = np.where(some, np.minimum(cnt, mh), 0.0)
             e_h = np.where(some[..., None], se / np.where(some, Wv, 1.0)[..., None], 0.0)
+            v_h = np.where(some, sv / np.where(some, Wv, 1.0), 0.0)  # the cap bounds the count, not the variance
         total = n_h + n_c
         with np.errstate(invalid="ignore", over="ignore"):
             e_out = (n_h[..., None] * e_h + n_c[..., None] * e) / np.where(total > 0, total, 1.0)[..., None]
@@ -211,7 +285,21 @@ class NumpyOps:
             count = np.where((h >= hmin) & np.isfinite(e_out).all(-1), total, 0.0)
             col_out = np.concatenate([e_out, count[..., None]], axis=-1).astype(np.float32)
             geo_out = np.concatenate([n, z[..., None]], axis=-1).astype(np.float32)
-        return out, (col_out, geo_out), margin
+        if not with_var:
+            return out, (col_out, geo_out), margin
+        v_c = np.asarray(variance_now, dtype=np.float64)
+        if v_c.shape != (H, W):
+            raise ValueError("variance_now must be [H, W]")
+        with np.errstate(invalid="ignore", over="ignore"):
+            v_c = np.where(v_c > 0.0, v_c, 0.0)  # a NaN or negative variance: 0
+            div = np.where(total > 0, total, 1.0)
+            a, b = n_h / div, n_c / div
+            # a term whose count is 0 is dropped, not multiplied (0 inf); no history: b = 1, v_c itself
+            v_out = np.where(n_h > 0, (a * a) * np.where(n_h > 0, v_h, 0.0), 0.0) \
+                + np.where(n_c > 0, (b * b) * np.where(n_c > 0, v_c, 0.0), 0.0)
+            v_out = np.where(total > 0, v_out, 0.0)
+            var_out = np.where(count > 0, v_out, 0.0).astype(np.float32)
+        return out, (col_out, geo_out, var_out), v_out, margin
 
 
 class HipOps:
@@ -255,6 +343,42 @@ class HipOps:
             C.byref(p) if p is not None else None, C.c_void_p(history_out.data_ptr()),
             C.c_void_p(out.data_ptr()), C.c_void_p(self.stream.cuda_stream)))
         return out, history_out
+
+    def history_variance_bytes(self, frame):
+        n = C.c_int64(0)
+        check(self.lib.rt_history_variance_bytes(C.byref(frame), C.byref(n)))
+        return n.value
+
+    def variance_history(self, frame):
+        """A variance-history tensor for `frame`."""
+        t = self.torch
+        with t.cuda.stream(self.stream):
+            return t.empty((self.history_variance_bytes(frame),), dtype=t.uint8, device=self.device)
+
+    def temporal_variance(self, frame_now, rgb, scale, tile_strata, strata_now, guides, guide_strata, variance_now,
+                          frame_prev=None, history_prev=None, params=None, history_out=None, out=None,
+                          variance_out=None):
+        """rt_temporal_variance_device -> (out [H, W, 3] float64, history_out uint8, variance_out [H, W] float64)."""
+        t = self.torch
+        h, w = frame_now.image_height, frame_now.image_width
+        if history_out is None:
+            history_out = self.variance_history(frame_now)
+        with t.cuda.stream(self.stream):
+            if out is None:
+                out = t.empty((h, w, 3), dtype=t.float64, device=self.device)
+            if variance_out is None:
+                variance_out = t.empty((h, w), dtype=t.float64, device=self.device)
+        p = abi.temporal_params(params)
+        check(self.lib.rt_temporal_variance_device(
+            C.byref(frame_now), C.c_void_p(rgb.data_ptr()), C.c_double(scale),
+            C.c_void_p(tile_strata.data_ptr() if tile_strata is not None else 0), int(strata_now),
+            C.c_void_p(guides.data_ptr()), int(guide_strata),
+            C.byref(frame_prev) if frame_prev is not None else None,
+            C.c_void_p(history_prev.data_ptr() if history_prev is not None else 0),
+            C.c_void_p(variance_now.data_ptr()), C.byref(p) if p is not None else None,
+            C.c_void_p(history_out.data_ptr()), C.c_void_p(out.data_ptr()), C.c_void_p(variance_out.data_ptr()),
+            C.c_void_p(self.stream.cuda_stream)))
+        return out, history_out, variance_out
 
 
 class TemporalDisplay:
@@ -367,3 +491,88 @@ class TemporalDisplay:
     def clear(self):
         """Forget the history (the scene changed): the next frames start from the samples alone."""
         self.frame_prev = self._shown = None
+
+
+class TemporalVarianceDisplay(TemporalDisplay):
+    """TemporalDisplay and VarianceGuidedDisplay composed: the variance of the
+    displayed estimate travels across camera moves with its colour, and the
+    variance-guided filter runs on the blend with the blend's own variance --
+    a blend that holds 64 strata of history is filtered as a 64-strata frame,
+    not as the 1-stratum frame the new pose has so far.
+
+    image() is three calls on the renderer's stream:
+     1. the current variance: rt_denoise_variance_device with passes -1 and
+        device_variance_out = v_now -- over an AdaptiveRenderer the batch
+        moments where a tile has `min_batches` batches and the spatial estimate
+        elsewhere, over a ProgressiveRenderer the spatial estimate alone;
+     2. rt_temporal_variance_device: the blend, its variance v_out and the
+        displayed frame's variance history;
+     3. with `filter`, rt_denoise_given_variance_device(blend, scale 1, no tile
+        strata, v_out).
+    `denoise`: the filter's rt_denoise_variance_params.  step, blended, bytes,
+    bytes_into, reset (the history swap), clear and has_history are
+    TemporalDisplay's; a frame of another size drops the history.  variance()
+    is the displayed frame's variance plane ([H, W] float64): the filter's
+    final v, or v_out with filter off.  Every buffer is allocated once per
+    frame size.
+
+        ar = adaptive.for_renderer(R, frame, seed=5, threshold=0, batch_strata=4)
+        tv = TemporalVarianceDisplay(ar)
+        pipe = progressive.DisplayPipeline(tv, bytes_fn=tv.bytes_into)
+    """
+
+    def __init__(self, pr, guide_strata=16, params=None, denoise=None, filter=True):
+        self.dd = VarianceGuidedDisplay(pr, guide_strata=guide_strata, params=denoise)
+        self.pr = pr
+        self.torch = self.dd.torch
+        self.stream = pr.stream
+        self.params = abi.temporal_params(params)
+        self.filter = bool(filter)
+        self.ops = HipOps(pr.acc.device, self.stream)
+        self._adaptive = self.dd._adaptive
+        # call 1: the filter's own parameters, no pass
+        q = self.dd.params
+        self._estimate = abi.DenoiseVarianceParams.from_buffer_copy(q) if q is not None \
+            else abi.DenoiseVarianceParams()
+        self._estimate.passes = -1
+        self._allocate()
+
+    def _allocate(self):
+        t, f = self.torch, self.pr.frame
+        self.hist = [self.ops.variance_history(f), self.ops.variance_history(f)]
+        with t.cuda.stream(self.stream):
+            self.blend = t.empty((f.image_height, f.image_width, 3), dtype=t.float64, device=self.pr.acc.device)
+            self.v_now = t.zeros((f.image_height, f.image_width), dtype=t.float64, device=self.pr.acc.device)
+            self.v_out = t.zeros((f.image_height, f.image_width), dtype=t.float64, device=self.pr.acc.device)
+        self._shape = (f.image_width, f.image_height)
+        self.frame_prev = None
+        self._shown = None
+        self._filtered = False
+
+    def blended(self):
+        """The blend alone; writes v_out and the displayed frame's variance history."""
+        dd, pr, ad = self.dd, self.pr, self._adaptive
+        dd._catch_up()
+        g = max(1, dd.guides_done)
+        scale, strata = (1.0, pr.tile_strata) if ad else (pr.scale, None)
+        dd.ops.denoise_variance(pr.frame, pr.acc, scale, strata, dd.guides, g, pr.s1 if ad else None,
+                                pr.s2 if ad else None, pr.batch_strata if ad else 0, self._estimate, dd.workspace,
+                                dd.out, self.v_now)
+        self.ops.temporal_variance(pr.frame, pr.acc, scale, strata, self.samples_taken, dd.guides, g, self.v_now,
+                                   self.frame_prev, self.hist[0] if self.has_history else None, self.params,
+                                   self.hist[1], self.blend, self.v_out)
+        self._shown = abi.Frame.from_buffer_copy(pr.frame)
+        self._filtered = False
+        return self.blend
+
+    def image(self):
+        img = self.blended()
+        if not self.filter:
+            return img
+        dd = self.dd
+        self._filtered = True
+        return dd.ops.denoise_given_variance(self.pr.frame, img, 1.0, None, dd.guides, max(1, dd.guides_done),
+                                             self.v_out, dd.params, dd.workspace, dd.out, dd.var)
+
+    def variance(self):
+        return self.dd.var if self._filtered else self.v_out
