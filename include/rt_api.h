@@ -903,6 +903,58 @@ int rt_multi_gather_ms(rt_multi *multi, double *ms);
 
 int rt_multi_destroy(rt_multi *multi);
 
+/* ---- guided sampling (one function added under ABI 5: no struct or signature
+   above changed) ------------------------------------------------------------
+   rt_adaptive_select_device retires a tile by the new pose's own batch
+   moments; after a camera move that is min_batches batches for every tile,
+   whatever history the display carried over.  This rule retires by the error
+   of the displayed estimate instead: the blend and the variance that
+   rt_temporal_variance_device writes (rtx/guided.py drives it and states it in
+   NumPy, NumpyOps.select; DESIGN.md "Guided sampling"). */
+
+/* The rule's defaults (the threshold has none): floor in demodulated units,
+   the unit of e = c / a_d. */
+#define RT_GUIDED_FLOOR 1e-2
+#define RT_GUIDED_MIN_COUNT 8
+
+/* device_tiles_out = the tiles of device_tiles_in[0 .. n_in) that still need
+   samples, in input order; *device_count_out = their number (4 bytes).
+   device_history is the variance history rt_temporal_variance_device wrote for
+   this frame, of which only the col plane (e.r, e.g, e.b, count; fp32) is
+   read; device_variance is that call's device_variance_out ([H][W] doubles).
+   Per pixel p inside the image, in fp64:
+     y = 0.2126 e.r + 0.7152 e.g + 0.0722 e.b;
+     v = device_variance[p], 0 when that is NaN or negative;
+     rel = sqrt(v) / (y + floor), +inf when a channel of e is not finite or
+           the quotient is NaN;
+     count_p = max(col.count, n_c), n_c the strata of the pixel's tile
+           (max(device_tile_strata[t], 0)), or strata_now without tile strata:
+           the stored count is 0 where the hit fraction is below hit_min, and
+           such a pixel still holds its own samples.
+   Per listed tile t (entries are clamped into [0, tiles - 1]): e_t = the mean
+   of rel and c_t = the minimum of count_p over the tile's pixels inside the
+   image.  The tile is dropped when c_t >= min_count and e_t <= threshold (a
+   NaN e_t keeps it): a tile with one pixel that found no history has
+   c_t = n_c and must earn min_count samples at the new pose.
+   device_tile_error[t] = e_t and device_tile_count[t] = c_t for the listed
+   tiles where those arrays ([tiles] doubles) are given; either may be NULL.
+   The 64-lane sum is a butterfly: e_t agrees with a sequential sum to
+   rounding, and the same inputs give the same bits again (no atomics).
+   n_in = 0 writes a count of 0 and nothing else.  Asynchronous on hip_stream;
+   needs no rt_scene, allocates nothing, keeps no state; runs on the current
+   device.  The history, the variance, the strata and the input list are only
+   read.  RT_ERR_INVALID, before anything is queued: a null frame,
+   device_history, device_variance, device_tiles_out or device_count_out, or a
+   null device_tiles_in with n_in > 0; an empty frame; n_in < 0 or above the
+   frame's tile count; a history that is not 256-B aligned;
+   device_tiles_out == device_tiles_in; a NaN threshold, floor or min_count;
+   floor <= 0; strata_now < 0. */
+int rt_guided_select_device(const rt_frame *frame, const void *device_history, const double *device_variance,
+                            const int32_t *device_tile_strata, int32_t strata_now, double threshold,
+                            double floor, double min_count, const int32_t *device_tiles_in, int32_t n_in,
+                            int32_t *device_tiles_out, int32_t *device_count_out, double *device_tile_error,
+                            double *device_tile_count, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,7 @@
 // rt_adaptive.hip — device side of adaptive sampling (rt_render_tiles_device,
 // rt_adaptive_update_device, rt_adaptive_select_device,
-// rt_to_bytes_tiles_device; host side in rt_api.cpp, driver in rtx/adaptive.py).
+// rt_to_bytes_tiles_device, rt_guided_select_device; host side in rt_api.cpp,
+// drivers in rtx/adaptive.py and rtx/guided.py).
 //
 // The render kernel is untouched: a tile-list launch hands it the caller's
 // list, copied and clamped here, as its dispatch order (DLaunch.tile_order).
@@ -87,6 +88,51 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock)
     const bool retire = nb >= max(2, min_batches) && e <= threshold;
     out[k] = retire ? -1 : t;
     if (tile_error != nullptr) tile_error[t] = e;
+  }
+}
+
+// rt_guided_select_device's rule (rtx/guided.py NumpyOps.select states it): one
+// wavefront per tile of the input list, one lane per pixel; a 16-B load of the
+// displayed frame's col plane (e.r, e.g, e.b, count) and an 8-B load of its
+// variance per lane.  The tile's flag goes into out[k] as adaptive_error_kernel
+// writes it, for the same compaction.
+__global__ void __launch_bounds__(64 * kWavesPerBlock)
+    guided_error_kernel(const float4 *col, const double *variance, const int32_t *tile_strata, int strata_now,
+                        int W, int H, int tiles_x, int tiles, double threshold, double floor_, double min_count,
+                        const int32_t *list, int n_in, int32_t *out, double *tile_error, double *tile_count) {
+  const int lane = threadIdx.x & 63;
+  const int k = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+  if (k >= n_in) return; // wave-uniform
+  const int t = clamp_tile(list[k], tiles);
+  const double n_c = (double)(tile_strata != nullptr ? max(tile_strata[t], 0) : strata_now);
+  const int x0 = (t % tiles_x) * 8, y0 = (t / tiles_x) * 8;
+  const int i = x0 + (lane & 7), j = y0 + (lane >> 3);
+  double rel = 0.0, cnt = __builtin_huge_val(); // what a lane outside the image contributes
+  if (i < W && j < H) {
+    const size_t p = (size_t)j * W + i;
+    const float4 c = col[p];
+    const double r = (double)c.x, g = (double)c.y, b = (double)c.z, stored = (double)c.w;
+    const double y = 0.2126 * r + 0.7152 * g + 0.0722 * b;
+    double v = variance[p];
+    v = v > 0.0 ? v : 0.0; // a NaN or negative variance: 0
+    rel = sqrt(v) / (y + floor_);
+    // (x - x) is 0 for a finite x and NaN otherwise
+    if (r - r != 0.0 || g - g != 0.0 || b - b != 0.0 || rel != rel) rel = __builtin_huge_val();
+    cnt = stored > n_c ? stored : n_c; // a stored count of 0 (or NaN): the pixel's own samples
+  }
+  // 64-lane butterflies: the sum of rel, the minimum of the counts
+  for (int off = 32; off > 0; off >>= 1) {
+    rel += __shfl_xor(rel, off);
+    const double other = __shfl_xor(cnt, off);
+    cnt = other < cnt ? other : cnt;
+  }
+  if (lane == 0) {
+    const int n_px = min(8, W - x0) * min(8, H - y0);
+    const double e = rel / (double)n_px;
+    const bool drop = cnt >= min_count && e <= threshold; // a NaN error keeps the tile
+    out[k] = drop ? -1 : t;
+    if (tile_error != nullptr) tile_error[t] = e;
+    if (tile_count != nullptr) tile_count[t] = cnt;
   }
 }
 
@@ -192,6 +238,24 @@ extern "C" hipError_t rtk_launch_adaptive_select(const double *s1, const double 
     if (e != hipSuccess) return e;
   }
   // n_in 0: the loop body never runs, the count becomes 0
+  hipLaunchKernelGGL(adaptive_compact_kernel, dim3(1), dim3(kScanThreads), 0, stream, out, n_in, count_out);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t rtk_launch_guided_select(const void *history, const double *variance,
+                                               const int32_t *tile_strata, int strata_now, int W, int H,
+                                               double threshold, double floor_, double min_count,
+                                               const int32_t *list, int n_in, int32_t *out, int32_t *count_out,
+                                               double *tile_error, double *tile_count, hipStream_t stream) {
+  const int tiles_x = (W + 7) / 8, tiles = tiles_x * ((H + 7) / 8);
+  if (n_in > 0) {
+    // the col plane is the history's first: 256-B aligned (checked by the caller), so every float4 is 16-B aligned
+    hipLaunchKernelGGL(guided_error_kernel, dim3(blocks_of(n_in, kWavesPerBlock)), dim3(64 * kWavesPerBlock), 0,
+                       stream, (const float4 *)history, variance, tile_strata, strata_now, W, H, tiles_x, tiles,
+                       threshold, floor_, min_count, list, n_in, out, tile_error, tile_count);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
   hipLaunchKernelGGL(adaptive_compact_kernel, dim3(1), dim3(kScanThreads), 0, stream, out, n_in, count_out);
   return hipGetLastError();
 }

@@ -925,6 +925,31 @@ int rt_adaptive_select_device(const double *device_s1, const double *device_s2,
   return RT_OK;
 }
 
+int rt_guided_select_device(const rt_frame *f, const void *device_history, const double *device_variance,
+                            const int32_t *device_tile_strata, int32_t strata_now, double threshold, double floor,
+                            double min_count, const int32_t *device_tiles_in, int32_t n_in,
+                            int32_t *device_tiles_out, int32_t *device_count_out, double *device_tile_error,
+                            double *device_tile_count, void *hip_stream) {
+  int64_t tiles = 0;
+  if (int rc = frame_tiles(f, tiles)) return rc;
+  if (!device_history || !device_variance || !device_tiles_out || !device_count_out)
+    return set_err(RT_ERR_INVALID, "null argument");
+  if (n_in < 0 || n_in > tiles) return set_err(RT_ERR_INVALID, "n_in outside [0, tiles of the frame]");
+  if (n_in > 0 && !device_tiles_in) return set_err(RT_ERR_INVALID, "null tile list");
+  if (((uintptr_t)device_history & 255) != 0) return set_err(RT_ERR_INVALID, "a history must be 256-B aligned");
+  if (device_tiles_in == device_tiles_out) return set_err(RT_ERR_INVALID, "tiles_out must not alias tiles_in");
+  if (threshold != threshold || floor != floor || min_count != min_count)
+    return set_err(RT_ERR_INVALID, "a guided-selection parameter is NaN");
+  if (!(floor > 0.0)) return set_err(RT_ERR_INVALID, "floor must be > 0");
+  if (strata_now < 0) return set_err(RT_ERR_INVALID, "strata_now must be >= 0");
+  hipError_t e = rtk_launch_guided_select(device_history, device_variance, device_tile_strata, strata_now,
+                                          f->image_width, f->image_height, threshold, floor, min_count,
+                                          device_tiles_in, n_in, device_tiles_out, device_count_out,
+                                          device_tile_error, device_tile_count, (hipStream_t)hip_stream);
+  if (e != hipSuccess) return hip_err(e, "guided select launch");
+  return RT_OK;
+}
+
 int rt_to_bytes_tiles_device(const double *device_rgb, const int32_t *device_tile_strata, const rt_frame *f,
                              uint8_t *device_bytes, void *hip_stream) {
   int64_t tiles = 0;

@@ -48,6 +48,13 @@ hipError_t rtk_launch_adaptive_select(const double *s1, const double *s2, const 
                                       int32_t *count_out, double *tile_error, hipStream_t stream);
 hipError_t rtk_launch_to_bytes_tiles(const double *rgb, const int32_t *tile_strata, int W, int H, uint8_t *bytes,
                                      hipStream_t stream);
+// guided sampling: history = a variance history (its col plane is read), variance = [H][W] doubles;
+// tile_strata may be null (then strata_now counts); tile_error / tile_count may be null
+hipError_t rtk_launch_guided_select(const void *history, const double *variance, const int32_t *tile_strata,
+                                    int strata_now, int W, int H, double threshold, double floor_,
+                                    double min_count, const int32_t *list, int n_in, int32_t *out,
+                                    int32_t *count_out, double *tile_error, double *tile_count,
+                                    hipStream_t stream);
 
 // ---- rt_guides.hip: first-hit guide sums [rows][W][8] (P: launch_geometry's fields; no plan)
 hipError_t rtk_launch_guides(const DScene *S, const DCamera *C, const DLaunch *P, double *out,

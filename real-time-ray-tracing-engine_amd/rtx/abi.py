@@ -224,6 +224,11 @@ def temporal_params(p=None):
     return out
 
 
+# include/rt_api.h RT_GUIDED_*: the guided selection's defaults (tests/test_guided.py
+# reads the header's values and compares)
+RT_GUIDED_FLOOR, RT_GUIDED_MIN_COUNT = 1e-2, 8
+
+
 def tuning(t=None):
     """A Tuning from None (the default), a Tuning, or a dict of its fields."""
     if t is None or isinstance(t, Tuning):
@@ -250,4 +255,5 @@ EXPORTS = (
     "rt_history_bytes", "rt_temporal_device",
     "rt_denoise_variance_workspace_bytes", "rt_denoise_variance_device",
     "rt_history_variance_bytes", "rt_temporal_variance_device", "rt_denoise_given_variance_device",
+    "rt_guided_select_device",
 )

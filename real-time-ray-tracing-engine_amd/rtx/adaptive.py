@@ -226,6 +226,16 @@ class AdaptiveRenderer:
         self.strata_done += n
         return n
 
+    def reselect(self, fn):
+        """A selection rule from outside (rtx.guided): fn(tiles_in, n_in,
+        tiles_out) -> kept writes the tiles of tiles_in[:n_in] that stay, in
+        order, into tiles_out; the lists are swapped and n_active set.
+        Returns the number kept.  step()'s own rule is untouched."""
+        tiles, out = self._lists[self._cur], self._lists[self._cur ^ 1]
+        self.n_active = int(fn(tiles, self.n_active, out))
+        self._cur ^= 1
+        return self.n_active
+
     def image(self):
         """The displayed radiance: every pixel scaled by 1 / max(1, its tile's strata)."""
         return self.ops.image(self.acc, self.tile_strata, self.frame)

@@ -92,6 +92,9 @@ def load():
     L.rt_denoise_given_variance_device.argtypes = [P(abi.Frame), C.c_void_p, C.c_double, C.c_void_p, C.c_void_p,
                                                    C.c_int32, C.c_void_p, P(abi.DenoiseVarianceParams),
                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rt_guided_select_device.argtypes = [P(abi.Frame), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_double,
+                                          C.c_double, C.c_double, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]
     for name in abi.EXPORTS:
         getattr(L, name).restype = C.c_char_p if name == "rt_last_error" else C.c_int
     if L.rt_abi_version() != abi.RT_ABI_VERSION:
