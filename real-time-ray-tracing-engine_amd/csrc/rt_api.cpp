@@ -987,11 +987,110 @@ int rt_render_guides_device(rt_scene *s, const rt_frame *f, const rt_render_para
   return mark_last(s, st);
 }
 
-int rt_denoise_workspace_bytes(const rt_frame *f, int64_t *bytes) {
+// a byte range of device memory; a null pointer spans nothing
+struct Span {
+  uintptr_t begin, end;
+  Span(const void *p, size_t bytes) : begin((uintptr_t)p), end(p ? begin + bytes : 0) {}
+};
+static bool overlaps(Span a, Span b) { return a.begin < b.end && b.begin < a.end; }
+
+// the four *_bytes entry points: `size` of the frame's width and height
+static int frame_bytes(const rt_frame *f, int64_t *bytes, size_t (*size)(int, int)) {
   int64_t tiles = 0;
   if (int rc = frame_tiles(f, tiles)) return rc;
   if (!bytes) return set_err(RT_ERR_INVALID, "null argument");
-  *bytes = (int64_t)rtk_denoise_workspace_bytes(f->image_width, f->image_height);
+  *bytes = (int64_t)size(f->image_width, f->image_height);
+  return RT_OK;
+}
+
+int rt_denoise_workspace_bytes(const rt_frame *f, int64_t *bytes) {
+  return frame_bytes(f, bytes, rtk_denoise_workspace_bytes);
+}
+int rt_denoise_variance_workspace_bytes(const rt_frame *f, int64_t *bytes) {
+  return frame_bytes(f, bytes, rtk_denoise_variance_workspace_bytes);
+}
+
+// the launch's fields that every filter entry point takes as arguments; W, H: filter_check
+static FilterLaunch filter_fields(int kind, const double *device_rgb, double rgb_scale,
+                                  const int32_t *device_tile_strata, const double *device_guides,
+                                  int32_t guide_strata, void *device_workspace, double *device_out,
+                                  double *device_variance_out) {
+  FilterLaunch a{};
+  a.kind = kind;
+  a.rgb = device_rgb;
+  a.scale = rgb_scale;
+  a.tile_strata = device_tile_strata;
+  a.guides = device_guides;
+  a.guide_strata = guide_strata;
+  a.workspace = device_workspace;
+  a.out = device_out;
+  a.var_out = device_variance_out;
+  return a;
+}
+
+// what the filter entry points refuse, in one order: frame, nulls, guide_strata, RTK_FILTER_VARIANCE's
+// moments, workspace alignment, overlaps (a pointer a kind does not take is null and spans nothing)
+static int filter_check(const rt_frame *f, FilterLaunch &a) {
+  int64_t tiles = 0;
+  if (int rc = frame_tiles(f, tiles)) return rc;
+  if (!a.rgb || !a.guides || !a.workspace || !a.out || (a.kind == RTK_FILTER_GIVEN && !a.variance))
+    return set_err(RT_ERR_INVALID, "null argument");
+  if (a.guide_strata < 1) return set_err(RT_ERR_INVALID, "guide_strata must be >= 1");
+  if ((a.s1 == nullptr) != (a.s2 == nullptr))
+    return set_err(RT_ERR_INVALID, "device_s1 and device_s2 go together: both or neither");
+  if (a.s1 && !a.tile_strata) return set_err(RT_ERR_INVALID, "moments need device_tile_strata");
+  if (a.s1 && a.batch_strata < 1) return set_err(RT_ERR_INVALID, "moments need batch_strata >= 1");
+  if (((uintptr_t)a.workspace & 255) != 0) return set_err(RT_ERR_INVALID, "workspace must be 256-B aligned");
+  a.W = f->image_width;
+  a.H = f->image_height;
+  const size_t px = (size_t)a.W * a.H;
+  const Span ws(a.workspace, a.kind == RTK_FILTER_PLAIN ? rtk_denoise_workspace_bytes(a.W, a.H)
+                                                        : rtk_denoise_variance_workspace_bytes(a.W, a.H));
+  const Span out(a.out, px * 3 * sizeof(double)), vout(a.var_out, px * sizeof(double));
+  const Span vin(a.variance, px * sizeof(double));
+  if (overlaps(out, ws)) return set_err(RT_ERR_INVALID, "device_out overlaps the workspace");
+  if (overlaps(vout, ws)) return set_err(RT_ERR_INVALID, "device_variance_out overlaps the workspace");
+  if (overlaps(vout, out)) return set_err(RT_ERR_INVALID, "device_variance_out overlaps device_out");
+  if (overlaps(vin, ws)) return set_err(RT_ERR_INVALID, "device_variance overlaps the workspace");
+  if (overlaps(vin, out)) return set_err(RT_ERR_INVALID, "device_variance overlaps device_out");
+  if (overlaps(vin, vout)) return set_err(RT_ERR_INVALID, "device_variance overlaps device_variance_out");
+  return RT_OK;
+}
+
+// rt_denoise_params / rt_denoise_variance_params resolved into the launch: 0 = the default,
+// a sigma < 0 stays (off); sigma_c: the colour sigma or sigma_lum, dflt_c its default
+static int filter_params(int passes, int min_batches, double sigma_n, double sigma_z, double sigma_h,
+                         double sigma_c, double dflt_c, FilterLaunch &a) {
+  if (passes > RT_DENOISE_MAX_PASSES)
+    return set_err(RT_ERR_INVALID, "passes must be at most " + std::to_string(RT_DENOISE_MAX_PASSES));
+  const double sig[4] = {sigma_n, sigma_z, sigma_h, sigma_c};
+  for (double v : sig)
+    if (v != v) return set_err(RT_ERR_INVALID, "a sigma is NaN");
+  auto pick = [](double v, double dflt) { return v == 0.0 ? dflt : v; }; // < 0: off
+  a.passes = passes == 0 ? RT_DENOISE_PASSES : passes;
+  a.min_batches = std::max(2, min_batches == 0 ? RT_DENOISE_MIN_BATCHES : min_batches);
+  a.sigma_n = pick(sigma_n, RT_DENOISE_SIGMA_NORMAL);
+  a.sigma_z = pick(sigma_z, RT_DENOISE_SIGMA_DEPTH);
+  a.sigma_h = pick(sigma_h, RT_DENOISE_SIGMA_HIT);
+  a.sigma_c = pick(sigma_c, dflt_c);
+  return RT_OK;
+}
+static int filter_params(const rt_denoise_params *params, FilterLaunch &a) {
+  rt_denoise_params q{};
+  if (params) q = *params;
+  return filter_params(q.passes, 0, q.sigma_normal, q.sigma_depth, q.sigma_hit, q.sigma_color,
+                       RT_DENOISE_SIGMA_COLOR, a);
+}
+static int filter_params(const rt_denoise_variance_params *params, FilterLaunch &a) {
+  rt_denoise_variance_params q{};
+  if (params) q = *params;
+  return filter_params(q.passes, q.min_batches, q.sigma_normal, q.sigma_depth, q.sigma_hit, q.sigma_lum,
+                       RT_DENOISE_SIGMA_LUM, a);
+}
+
+static int filter_launch(const FilterLaunch &a, void *hip_stream, const char *what) {
+  hipError_t e = rtk_launch_filter(&a, (hipStream_t)hip_stream);
+  if (e != hipSuccess) return hip_err(e, what);
   return RT_OK;
 }
 
@@ -999,45 +1098,11 @@ int rt_denoise_device(const rt_frame *f, const double *device_rgb, double rgb_sc
                       const int32_t *device_tile_strata, const double *device_guides, int32_t guide_strata,
                       const rt_denoise_params *params, void *device_workspace, double *device_out,
                       void *hip_stream) {
-  int64_t tiles = 0;
-  if (int rc = frame_tiles(f, tiles)) return rc;
-  if (!device_rgb || !device_guides || !device_workspace || !device_out)
-    return set_err(RT_ERR_INVALID, "null argument");
-  if (guide_strata < 1) return set_err(RT_ERR_INVALID, "guide_strata must be >= 1");
-  if (((uintptr_t)device_workspace & 255) != 0) return set_err(RT_ERR_INVALID, "workspace must be 256-B aligned");
-  {
-    const uintptr_t w0 = (uintptr_t)device_workspace;
-    const uintptr_t w1 = w0 + rtk_denoise_workspace_bytes(f->image_width, f->image_height);
-    const uintptr_t o0 = (uintptr_t)device_out;
-    const uintptr_t o1 = o0 + (size_t)f->image_width * f->image_height * 3 * sizeof(double);
-    if (o0 < w1 && w0 < o1) return set_err(RT_ERR_INVALID, "device_out overlaps the workspace");
-  }
-  rt_denoise_params q{};
-  if (params) q = *params;
-  if (q.passes > RT_DENOISE_MAX_PASSES)
-    return set_err(RT_ERR_INVALID, "passes must be at most " + std::to_string(RT_DENOISE_MAX_PASSES));
-  const double sig[4] = {q.sigma_normal, q.sigma_depth, q.sigma_hit, q.sigma_color};
-  for (double v : sig)
-    if (v != v) return set_err(RT_ERR_INVALID, "a sigma is NaN");
-  auto pick = [](double v, double dflt) { return v == 0.0 ? dflt : v; }; // < 0: off
-  const int passes = q.passes == 0 ? RT_DENOISE_PASSES : q.passes;
-  hipError_t e = rtk_launch_denoise(f->image_width, f->image_height, device_rgb, rgb_scale, device_tile_strata,
-                                    device_guides, guide_strata, passes,
-                                    pick(q.sigma_normal, RT_DENOISE_SIGMA_NORMAL),
-                                    pick(q.sigma_depth, RT_DENOISE_SIGMA_DEPTH),
-                                    pick(q.sigma_hit, RT_DENOISE_SIGMA_HIT),
-                                    pick(q.sigma_color, RT_DENOISE_SIGMA_COLOR), device_workspace, device_out,
-                                    (hipStream_t)hip_stream);
-  if (e != hipSuccess) return hip_err(e, "denoise launch");
-  return RT_OK;
-}
-
-int rt_denoise_variance_workspace_bytes(const rt_frame *f, int64_t *bytes) {
-  int64_t tiles = 0;
-  if (int rc = frame_tiles(f, tiles)) return rc;
-  if (!bytes) return set_err(RT_ERR_INVALID, "null argument");
-  *bytes = (int64_t)rtk_denoise_variance_workspace_bytes(f->image_width, f->image_height);
-  return RT_OK;
+  FilterLaunch a = filter_fields(RTK_FILTER_PLAIN, device_rgb, rgb_scale, device_tile_strata, device_guides,
+                                 guide_strata, device_workspace, device_out, nullptr);
+  if (int rc = filter_check(f, a)) return rc;
+  if (int rc = filter_params(params, a)) return rc;
+  return filter_launch(a, hip_stream, "denoise launch");
 }
 
 int rt_denoise_variance_device(const rt_frame *f, const double *device_rgb, double rgb_scale,
@@ -1046,56 +1111,31 @@ int rt_denoise_variance_device(const rt_frame *f, const double *device_rgb, doub
                                int32_t batch_strata, const rt_denoise_variance_params *params,
                                void *device_workspace, double *device_out, double *device_variance_out,
                                void *hip_stream) {
-  int64_t tiles = 0;
-  if (int rc = frame_tiles(f, tiles)) return rc;
-  if (!device_rgb || !device_guides || !device_workspace || !device_out)
-    return set_err(RT_ERR_INVALID, "null argument");
-  if (guide_strata < 1) return set_err(RT_ERR_INVALID, "guide_strata must be >= 1");
-  if ((device_s1 == nullptr) != (device_s2 == nullptr))
-    return set_err(RT_ERR_INVALID, "device_s1 and device_s2 go together: both or neither");
-  if (device_s1 && !device_tile_strata) return set_err(RT_ERR_INVALID, "moments need device_tile_strata");
-  if (device_s1 && batch_strata < 1) return set_err(RT_ERR_INVALID, "moments need batch_strata >= 1");
-  if (((uintptr_t)device_workspace & 255) != 0) return set_err(RT_ERR_INVALID, "workspace must be 256-B aligned");
-  {
-    const size_t px = (size_t)f->image_width * f->image_height;
-    const uintptr_t w0 = (uintptr_t)device_workspace;
-    const uintptr_t w1 = w0 + rtk_denoise_variance_workspace_bytes(f->image_width, f->image_height);
-    const uintptr_t o0 = (uintptr_t)device_out, o1 = o0 + px * 3 * sizeof(double);
-    const uintptr_t v0 = (uintptr_t)device_variance_out, v1 = v0 + px * sizeof(double);
-    if (o0 < w1 && w0 < o1) return set_err(RT_ERR_INVALID, "device_out overlaps the workspace");
-    if (device_variance_out && v0 < w1 && w0 < v1)
-      return set_err(RT_ERR_INVALID, "device_variance_out overlaps the workspace");
-    if (device_variance_out && v0 < o1 && o0 < v1)
-      return set_err(RT_ERR_INVALID, "device_variance_out overlaps device_out");
-  }
-  rt_denoise_variance_params q{};
-  if (params) q = *params;
-  if (q.passes > RT_DENOISE_MAX_PASSES)
-    return set_err(RT_ERR_INVALID, "passes must be at most " + std::to_string(RT_DENOISE_MAX_PASSES));
-  const double sig[4] = {q.sigma_normal, q.sigma_depth, q.sigma_hit, q.sigma_lum};
-  for (double v : sig)
-    if (v != v) return set_err(RT_ERR_INVALID, "a sigma is NaN");
-  auto pick = [](double v, double dflt) { return v == 0.0 ? dflt : v; }; // < 0: off
-  const int passes = q.passes == 0 ? RT_DENOISE_PASSES : q.passes;
-  const int min_batches = std::max(2, q.min_batches == 0 ? RT_DENOISE_MIN_BATCHES : q.min_batches);
-  hipError_t e = rtk_launch_denoise_variance(
-      f->image_width, f->image_height, device_rgb, rgb_scale, device_tile_strata, device_guides, guide_strata,
-      device_s1, device_s2, batch_strata, min_batches, passes, pick(q.sigma_normal, RT_DENOISE_SIGMA_NORMAL),
-      pick(q.sigma_depth, RT_DENOISE_SIGMA_DEPTH), pick(q.sigma_hit, RT_DENOISE_SIGMA_HIT),
-      pick(q.sigma_lum, RT_DENOISE_SIGMA_LUM), device_workspace, device_out, device_variance_out,
-      (hipStream_t)hip_stream);
-  if (e != hipSuccess) return hip_err(e, "variance-guided denoise launch");
-  return RT_OK;
+  FilterLaunch a = filter_fields(RTK_FILTER_VARIANCE, device_rgb, rgb_scale, device_tile_strata, device_guides,
+                                 guide_strata, device_workspace, device_out, device_variance_out);
+  a.s1 = device_s1;
+  a.s2 = device_s2;
+  a.batch_strata = batch_strata;
+  if (int rc = filter_check(f, a)) return rc;
+  if (int rc = filter_params(params, a)) return rc;
+  return filter_launch(a, hip_stream, "variance-guided denoise launch");
+}
+
+int rt_denoise_given_variance_device(const rt_frame *f, const double *device_rgb, double rgb_scale,
+                                     const int32_t *device_tile_strata, const double *device_guides,
+                                     int32_t guide_strata, const double *device_variance,
+                                     const rt_denoise_variance_params *params, void *device_workspace,
+                                     double *device_out, double *device_variance_out, void *hip_stream) {
+  FilterLaunch a = filter_fields(RTK_FILTER_GIVEN, device_rgb, rgb_scale, device_tile_strata, device_guides,
+                                 guide_strata, device_workspace, device_out, device_variance_out);
+  a.variance = device_variance;
+  if (int rc = filter_check(f, a)) return rc;
+  if (int rc = filter_params(params, a)) return rc;
+  return filter_launch(a, hip_stream, "given-variance denoise launch");
 }
 
 // ---------------------------------------------------------------- temporal reprojection
-int rt_history_bytes(const rt_frame *f, int64_t *bytes) {
-  int64_t tiles = 0;
-  if (int rc = frame_tiles(f, tiles)) return rc;
-  if (!bytes) return set_err(RT_ERR_INVALID, "null argument");
-  *bytes = (int64_t)rtk_history_bytes(f->image_width, f->image_height);
-  return RT_OK;
-}
+int rt_history_bytes(const rt_frame *f, int64_t *bytes) { return frame_bytes(f, bytes, rtk_history_bytes); }
 
 // what rt_temporal_device and rt_temporal_variance_device refuse alike; hb: the bytes of one history
 static int temporal_args(const rt_frame *f, const double *device_rgb, const int32_t *device_tile_strata,
@@ -1113,16 +1153,10 @@ static int temporal_args(const rt_frame *f, const double *device_rgb, const int3
     return set_err(RT_ERR_INVALID, "frame_prev has another size than frame_now");
   if (((uintptr_t)device_history_out & 255) != 0 || ((uintptr_t)device_history_prev & 255) != 0)
     return set_err(RT_ERR_INVALID, "a history must be 256-B aligned");
-  {
-    const uintptr_t a0 = (uintptr_t)device_history_out, a1 = a0 + hb;
-    const uintptr_t b0 = (uintptr_t)device_history_prev, b1 = b0 + hb;
-    const uintptr_t o0 = (uintptr_t)device_out;
-    const uintptr_t o1 = o0 + (size_t)f->image_width * f->image_height * 3 * sizeof(double);
-    if (device_history_prev && a0 < b1 && b0 < a1)
-      return set_err(RT_ERR_INVALID, "device_history_out overlaps device_history_prev");
-    if ((o0 < a1 && a0 < o1) || (device_history_prev && o0 < b1 && b0 < o1))
-      return set_err(RT_ERR_INVALID, "device_out overlaps a history");
-  }
+  const Span hout(device_history_out, hb), hprev(device_history_prev, hb);
+  const Span out(device_out, (size_t)f->image_width * f->image_height * 3 * sizeof(double));
+  if (overlaps(hout, hprev)) return set_err(RT_ERR_INVALID, "device_history_out overlaps device_history_prev");
+  if (overlaps(out, hout) || overlaps(out, hprev)) return set_err(RT_ERR_INVALID, "device_out overlaps a history");
   q = rt_temporal_params{};
   if (params) q = *params;
   if (q.max_history < 0) return set_err(RT_ERR_INVALID, "max_history must be >= 0");
@@ -1153,11 +1187,7 @@ int rt_temporal_device(const rt_frame *f, const double *device_rgb, double rgb_s
 
 // ---------------------------------------------------------------- temporal variance
 int rt_history_variance_bytes(const rt_frame *f, int64_t *bytes) {
-  int64_t tiles = 0;
-  if (int rc = frame_tiles(f, tiles)) return rc;
-  if (!bytes) return set_err(RT_ERR_INVALID, "null argument");
-  *bytes = (int64_t)rtk_history_variance_bytes(f->image_width, f->image_height);
-  return RT_OK;
+  return frame_bytes(f, bytes, rtk_history_variance_bytes);
 }
 
 int rt_temporal_variance_device(const rt_frame *f, const double *device_rgb, double rgb_scale,
@@ -1174,70 +1204,19 @@ int rt_temporal_variance_device(const rt_frame *f, const double *device_rgb, dou
   if (int rc = temporal_args(f, device_rgb, device_tile_strata, strata_now, device_guides, guide_strata, frame_prev,
                              device_history_prev, params, device_history_out, device_out, hb, q))
     return rc;
-  {
-    const size_t px = (size_t)f->image_width * f->image_height;
-    const uintptr_t a0 = (uintptr_t)device_history_out, a1 = a0 + hb;
-    const uintptr_t b0 = (uintptr_t)device_history_prev, b1 = b0 + hb;
-    const uintptr_t o0 = (uintptr_t)device_out, o1 = o0 + px * 3 * sizeof(double);
-    const uintptr_t n0 = (uintptr_t)device_variance_now, n1 = n0 + px * sizeof(double);
-    const uintptr_t v0 = (uintptr_t)device_variance_out, v1 = v0 + px * sizeof(double);
-    if ((v0 < a1 && a0 < v1) || (device_history_prev && v0 < b1 && b0 < v1))
-      return set_err(RT_ERR_INVALID, "device_variance_out overlaps a history");
-    if (v0 < n1 && n0 < v1) return set_err(RT_ERR_INVALID, "device_variance_out overlaps device_variance_now");
-    if (v0 < o1 && o0 < v1) return set_err(RT_ERR_INVALID, "device_variance_out overlaps device_out");
-  }
+  const size_t px = (size_t)f->image_width * f->image_height;
+  const Span vout(device_variance_out, px * sizeof(double));
+  if (overlaps(vout, Span(device_history_out, hb)) || overlaps(vout, Span(device_history_prev, hb)))
+    return set_err(RT_ERR_INVALID, "device_variance_out overlaps a history");
+  if (overlaps(vout, Span(device_variance_now, px * sizeof(double))))
+    return set_err(RT_ERR_INVALID, "device_variance_out overlaps device_variance_now");
+  if (overlaps(vout, Span(device_out, px * 3 * sizeof(double))))
+    return set_err(RT_ERR_INVALID, "device_variance_out overlaps device_out");
   hipError_t e = rtk_launch_temporal_variance(f, device_rgb, rgb_scale, device_tile_strata, strata_now,
                                               device_guides, guide_strata, frame_prev, device_history_prev,
                                               device_variance_now, &q, device_history_out, device_out,
                                               device_variance_out, (hipStream_t)hip_stream);
   if (e != hipSuccess) return hip_err(e, "temporal variance launch");
-  return RT_OK;
-}
-
-int rt_denoise_given_variance_device(const rt_frame *f, const double *device_rgb, double rgb_scale,
-                                     const int32_t *device_tile_strata, const double *device_guides,
-                                     int32_t guide_strata, const double *device_variance,
-                                     const rt_denoise_variance_params *params, void *device_workspace,
-                                     double *device_out, double *device_variance_out, void *hip_stream) {
-  int64_t tiles = 0;
-  if (int rc = frame_tiles(f, tiles)) return rc;
-  if (!device_rgb || !device_guides || !device_workspace || !device_out || !device_variance)
-    return set_err(RT_ERR_INVALID, "null argument");
-  if (guide_strata < 1) return set_err(RT_ERR_INVALID, "guide_strata must be >= 1");
-  if (((uintptr_t)device_workspace & 255) != 0) return set_err(RT_ERR_INVALID, "workspace must be 256-B aligned");
-  {
-    const size_t px = (size_t)f->image_width * f->image_height;
-    const uintptr_t w0 = (uintptr_t)device_workspace;
-    const uintptr_t w1 = w0 + rtk_denoise_variance_workspace_bytes(f->image_width, f->image_height);
-    const uintptr_t o0 = (uintptr_t)device_out, o1 = o0 + px * 3 * sizeof(double);
-    const uintptr_t v0 = (uintptr_t)device_variance_out, v1 = v0 + px * sizeof(double);
-    const uintptr_t g0 = (uintptr_t)device_variance, g1 = g0 + px * sizeof(double);
-    if (o0 < w1 && w0 < o1) return set_err(RT_ERR_INVALID, "device_out overlaps the workspace");
-    if (device_variance_out && v0 < w1 && w0 < v1)
-      return set_err(RT_ERR_INVALID, "device_variance_out overlaps the workspace");
-    if (device_variance_out && v0 < o1 && o0 < v1)
-      return set_err(RT_ERR_INVALID, "device_variance_out overlaps device_out");
-    if (g0 < w1 && w0 < g1) return set_err(RT_ERR_INVALID, "device_variance overlaps the workspace");
-    if (g0 < o1 && o0 < g1) return set_err(RT_ERR_INVALID, "device_variance overlaps device_out");
-    if (device_variance_out && g0 < v1 && v0 < g1)
-      return set_err(RT_ERR_INVALID, "device_variance overlaps device_variance_out");
-  }
-  rt_denoise_variance_params q{};
-  if (params) q = *params;
-  if (q.passes > RT_DENOISE_MAX_PASSES)
-    return set_err(RT_ERR_INVALID, "passes must be at most " + std::to_string(RT_DENOISE_MAX_PASSES));
-  const double sig[4] = {q.sigma_normal, q.sigma_depth, q.sigma_hit, q.sigma_lum};
-  for (double v : sig)
-    if (v != v) return set_err(RT_ERR_INVALID, "a sigma is NaN");
-  auto pick = [](double v, double dflt) { return v == 0.0 ? dflt : v; }; // < 0: off
-  const int passes = q.passes == 0 ? RT_DENOISE_PASSES : q.passes;
-  hipError_t e = rtk_launch_denoise_given_variance(
-      f->image_width, f->image_height, device_rgb, rgb_scale, device_tile_strata, device_guides, guide_strata,
-      device_variance, passes, pick(q.sigma_normal, RT_DENOISE_SIGMA_NORMAL),
-      pick(q.sigma_depth, RT_DENOISE_SIGMA_DEPTH), pick(q.sigma_hit, RT_DENOISE_SIGMA_HIT),
-      pick(q.sigma_lum, RT_DENOISE_SIGMA_LUM), device_workspace, device_out, device_variance_out,
-      (hipStream_t)hip_stream);
-  if (e != hipSuccess) return hip_err(e, "given-variance denoise launch");
   return RT_OK;
 }
 

@@ -60,28 +60,34 @@ hipError_t rtk_launch_guided_select(const void *history, const double *variance,
 hipError_t rtk_launch_guides(const DScene *S, const DCamera *C, const DLaunch *P, double *out,
                              hipStream_t stream);
 
-// ---- rt_denoise.hip: the a-trous filter (sigmas resolved: > 0 on, <= 0 off; passes < 0: none)
-size_t rtk_denoise_workspace_bytes(int W, int H);
-hipError_t rtk_launch_denoise(int W, int H, const double *rgb, double scale, const int32_t *tile_strata,
-                              const double *guides, int guide_strata, int passes, double sigma_n,
-                              double sigma_z, double sigma_h, double sigma_c, void *workspace, double *out,
-                              hipStream_t stream);
-
-// the variance-guided filter: s1 / s2 null = no moments; min_batches resolved (>= 2); sigma_l <= 0: term off;
-// var_out may be null
-size_t rtk_denoise_variance_workspace_bytes(int W, int H);
-hipError_t rtk_launch_denoise_variance(int W, int H, const double *rgb, double scale, const int32_t *tile_strata,
-                                       const double *guides, int guide_strata, const double *s1, const double *s2,
-                                       int batch_strata, int min_batches, int passes, double sigma_n,
-                                       double sigma_z, double sigma_h, double sigma_l, void *workspace,
-                                       double *out, double *var_out, hipStream_t stream);
-
-// the same passes on the caller's variance plane ([H][W] double): no estimation stage
-hipError_t rtk_launch_denoise_given_variance(int W, int H, const double *rgb, double scale,
-                                             const int32_t *tile_strata, const double *guides, int guide_strata,
-                                             const double *variance, int passes, double sigma_n, double sigma_z,
-                                             double sigma_h, double sigma_l, void *workspace, double *out,
-                                             double *var_out, hipStream_t stream);
+// ---- rt_denoise.hip: the a-trous filters, one launcher.  Sigmas resolved: > 0 on, <= 0 off; passes < 0: none
+size_t rtk_denoise_workspace_bytes(int W, int H);          // the plain layout
+size_t rtk_denoise_variance_workspace_bytes(int W, int H); // the variance layout (both variance kinds)
+enum {
+  RTK_FILTER_PLAIN = 0,    // rt_denoise_device
+  RTK_FILTER_VARIANCE = 1, // rt_denoise_variance_device: v from the moments and the spatial estimate
+  RTK_FILTER_GIVEN = 2     // rt_denoise_given_variance_device: v is the caller's plane, no estimation stage
+};
+struct FilterLaunch {
+  int kind;
+  int W, H;
+  const double *rgb;
+  double scale;
+  const int32_t *tile_strata;
+  const double *guides;
+  int guide_strata;
+  const double *s1, *s2; // VARIANCE: the batch moments, null = none
+  int batch_strata;
+  int min_batches;        // VARIANCE: resolved (>= 2)
+  const double *variance; // GIVEN: [H][W]
+  int passes;
+  double sigma_n, sigma_z, sigma_h;
+  double sigma_c; // PLAIN: the colour sigma; the variance kinds: sigma_l
+  void *workspace;
+  double *out;
+  double *var_out; // the variance kinds; may be null
+};
+hipError_t rtk_launch_filter(const FilterLaunch *args, hipStream_t stream);
 
 // ---- rt_temporal.hip: the temporal reprojection (params checked, may be null; prev /
 // history_prev both null: no history); the _variance pair takes histories with a var plane

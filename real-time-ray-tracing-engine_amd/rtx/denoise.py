@@ -112,17 +112,20 @@ def resolve_variance(params=None):
     return passes, max(2, mb), sn, sz, sh, None if sl < 0 else float(sl)
 
 
-def variance_workspace_bytes(frame):
-    """rt_denoise_variance_workspace_bytes: four float4 planes and one float
-    plane (68 B per pixel), each padded to 256 B."""
+def _workspace_bytes(frame, variance):
+    """Four float4 planes, each padded to 256 B; the variance layout: and one float plane."""
     n = frame.image_width * frame.image_height
-    return 4 * ((n * 16 + 255) & ~255) + ((n * 4 + 255) & ~255)
+    return 4 * ((n * 16 + 255) & ~255) + (((n * 4 + 255) & ~255) if variance else 0)
 
 
 def workspace_bytes(frame):
-    """rt_denoise_workspace_bytes: four float4 planes, each padded to 256 B."""
-    plane = (frame.image_width * frame.image_height * 16 + 255) & ~255
-    return 4 * plane
+    """rt_denoise_workspace_bytes: 64 B per pixel."""
+    return _workspace_bytes(frame, False)
+
+
+def variance_workspace_bytes(frame):
+    """rt_denoise_variance_workspace_bytes: 68 B per pixel."""
+    return _workspace_bytes(frame, True)
 
 
 def _pixel_scale(tile_strata, frame):
@@ -150,8 +153,8 @@ class NumpyOps:
     """rt_denoise_device and rt_denoise_variance_device on host arrays, in
     fp64: the statements of record."""
 
-    def workspace_bytes(self, frame):
-        return workspace_bytes(frame)
+    workspace_bytes = staticmethod(workspace_bytes)
+    variance_workspace_bytes = staticmethod(variance_workspace_bytes)
 
     def prepare(self, frame, rgb, scale, tile_strata, guides, guide_strata):
         """(e, a_d, n, z, h) of the definition above."""
@@ -232,9 +235,6 @@ class NumpyOps:
         return e * a_d
 
     # ---- the variance-guided filter (rt_denoise_variance_device) ----
-    def variance_workspace_bytes(self, frame):
-        return variance_workspace_bytes(frame)
-
     def blur3(self, v, ok):
         """v~: the 3x3 Gaussian (1/4, 1/2, 1/4 per axis) of v over the in-image
         pixels whose e is finite, renormalised; 0 where there is none."""
@@ -310,6 +310,10 @@ class NumpyOps:
         if s1 is not None:
             vm, use = self.moments_variance(frame, a_d, tile_strata, s1, s2, batch_strata, min_batches)
             v = np.where(use, vm, v)
+        return self._variance_passes(e, a_d, n, z, h, v, passes, sn, sz, sh, sl, with_variance)
+
+    def _variance_passes(self, e, a_d, n, z, h, v, passes, sn, sz, sh, sl, with_variance):
+        """The shared tail: v = 0 where e is not finite, the passes, out = e a_d."""
         v = np.where(np.isfinite(e).all(-1), v, 0.0)
         for k in range(passes):
             e, v = self.one_pass(e, n, z, h, k, sn, sz, sh, None, v, sl)
@@ -329,10 +333,7 @@ class NumpyOps:
             raise ValueError("variance must be [H, W]")
         with np.errstate(invalid="ignore"):
             v = np.where(v > 0.0, v, 0.0)
-        v = np.where(np.isfinite(e).all(-1), v, 0.0)
-        for k in range(passes):
-            e, v = self.one_pass(e, n, z, h, k, sn, sz, sh, None, v, sl)
-        return (e * a_d, v) if with_variance else e * a_d
+        return self._variance_passes(e, a_d, n, z, h, v, passes, sn, sz, sh, sl, with_variance)
 
     def bytes(self, image):
         return to_bytes(image)
@@ -351,56 +352,59 @@ class HipOps:
     def _sp(self):
         return C.c_void_p(self.stream.cuda_stream)
 
-    def workspace_bytes(self, frame):
-        n = C.c_int64(0)
-        check(self.lib.rt_denoise_workspace_bytes(C.byref(frame), C.byref(n)))
-        return n.value
+    @staticmethod
+    def _ptr(a):
+        """The device pointer of a tensor, null for None."""
+        return C.c_void_p(a.data_ptr() if a is not None else 0)
 
-    def workspace(self, frame):
-        """A workspace tensor for `frame` (torch allocations are 512-B aligned)."""
+    def _image(self, frame, out=None):
+        """`out`, or a new [H, W, 3] float64 image on the stream."""
+        if out is not None:
+            return out
         t = self.torch
         with t.cuda.stream(self.stream):
-            return t.empty((self.workspace_bytes(frame),), dtype=t.uint8, device=self.device)
+            return t.empty((frame.image_height, frame.image_width, 3), dtype=t.float64, device=self.device)
+
+    def _bytes(self, fn, frame):
+        n = C.c_int64(0)
+        check(fn(C.byref(frame), C.byref(n)))
+        return n.value
+
+    def _workspace(self, nbytes):
+        """A workspace tensor of `nbytes` (torch allocations are 512-B aligned)."""
+        t = self.torch
+        with t.cuda.stream(self.stream):
+            return t.empty((nbytes,), dtype=t.uint8, device=self.device)
+
+    def workspace_bytes(self, frame):
+        return self._bytes(self.lib.rt_denoise_workspace_bytes, frame)
+
+    def workspace(self, frame):
+        return self._workspace(self.workspace_bytes(frame))
+
+    def variance_workspace_bytes(self, frame):
+        return self._bytes(self.lib.rt_denoise_variance_workspace_bytes, frame)
+
+    def variance_workspace(self, frame):
+        return self._workspace(self.variance_workspace_bytes(frame))
 
     def denoise(self, frame, rgb, scale, tile_strata, guides, guide_strata, params=None, workspace=None,
                 out=None):
-        t = self.torch
-        if workspace is None:
-            workspace = self.workspace(frame)
-        if out is None:
-            with t.cuda.stream(self.stream):
-                out = t.empty((frame.image_height, frame.image_width, 3), dtype=t.float64, device=self.device)
+        ptr = self._ptr
+        workspace = self.workspace(frame) if workspace is None else workspace
+        out = self._image(frame, out)
         p = abi.denoise_params(params)
         check(self.lib.rt_denoise_device(
-            C.byref(frame), C.c_void_p(rgb.data_ptr()), C.c_double(scale),
-            C.c_void_p(tile_strata.data_ptr() if tile_strata is not None else 0),
-            C.c_void_p(guides.data_ptr()), int(guide_strata), C.byref(p) if p is not None else None,
-            C.c_void_p(workspace.data_ptr()), C.c_void_p(out.data_ptr()), self._sp()))
+            C.byref(frame), ptr(rgb), C.c_double(scale), ptr(tile_strata), ptr(guides), int(guide_strata),
+            C.byref(p) if p is not None else None, ptr(workspace), ptr(out), self._sp()))
         return out
-
-    def variance_workspace_bytes(self, frame):
-        n = C.c_int64(0)
-        check(self.lib.rt_denoise_variance_workspace_bytes(C.byref(frame), C.byref(n)))
-        return n.value
-
-    def variance_workspace(self, frame):
-        t = self.torch
-        with t.cuda.stream(self.stream):
-            return t.empty((self.variance_workspace_bytes(frame),), dtype=t.uint8, device=self.device)
 
     def denoise_variance(self, frame, rgb, scale, tile_strata, guides, guide_strata, s1=None, s2=None,
                          batch_strata=0, params=None, workspace=None, out=None, variance_out=None):
         """rt_denoise_variance_device; `variance_out` ([H, W] float64) takes the final variance plane."""
-        t = self.torch
-        if workspace is None:
-            workspace = self.variance_workspace(frame)
-        if out is None:
-            with t.cuda.stream(self.stream):
-                out = t.empty((frame.image_height, frame.image_width, 3), dtype=t.float64, device=self.device)
-
-        def ptr(a):
-            return C.c_void_p(a.data_ptr() if a is not None else 0)
-
+        ptr = self._ptr
+        workspace = self.variance_workspace(frame) if workspace is None else workspace
+        out = self._image(frame, out)
         p = abi.denoise_variance_params(params)
         check(self.lib.rt_denoise_variance_device(
             C.byref(frame), ptr(rgb), C.c_double(scale), ptr(tile_strata), ptr(guides), int(guide_strata),
@@ -411,16 +415,9 @@ class HipOps:
     def denoise_given_variance(self, frame, rgb, scale, tile_strata, guides, guide_strata, variance, params=None,
                                workspace=None, out=None, variance_out=None):
         """rt_denoise_given_variance_device: the passes on the caller's `variance` plane ([H, W] float64)."""
-        t = self.torch
-        if workspace is None:
-            workspace = self.variance_workspace(frame)
-        if out is None:
-            with t.cuda.stream(self.stream):
-                out = t.empty((frame.image_height, frame.image_width, 3), dtype=t.float64, device=self.device)
-
-        def ptr(a):
-            return C.c_void_p(a.data_ptr() if a is not None else 0)
-
+        ptr = self._ptr
+        workspace = self.variance_workspace(frame) if workspace is None else workspace
+        out = self._image(frame, out)
         p = abi.denoise_variance_params(params)
         check(self.lib.rt_denoise_given_variance_device(
             C.byref(frame), ptr(rgb), C.c_double(scale), ptr(tile_strata), ptr(guides), int(guide_strata),

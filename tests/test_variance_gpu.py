@@ -154,7 +154,8 @@ def test_luminance_term_off_is_rt_denoise_device_without_its_colour_term():
                            dict(passes=passes, sigma_color=-1)).cpu().numpy()
         got, _ = gpu_variance(f, rgb, 1.0, strata, guides, g, s1, s2, BATCH, dict(passes=passes, sigma_lum=-1))
         assert_close(got, want, "luminance off against rt_denoise_device, passes %d" % passes)
-        print("    bit-identical: %s" % np.array_equal(got, want))
+        # both are instances of one pass template (rt_denoise.hip pass_kernel): the same arithmetic
+        assert np.array_equal(got, want), "luminance off differs from rt_denoise_device, passes %d" % passes
 
 
 @pytest.mark.parametrize("name", ["cornell_fog", "bouncing_seed42"])

@@ -4,7 +4,14 @@ RTX_LIB names and save the raw fp64 sums to an .npy file -- for bit-identity
 checks between library variants (compare the files with --compare).
 
     RTX_LIB=... python tools/frame_dump.py --config C4 --width 480 --spp 64 --out a.npy
-    python tools/frame_dump.py --compare a.npy b.npy"""
+    python tools/frame_dump.py --compare a.npy b.npy
+
+--display instead runs the three display filters (rt_denoise_device,
+rt_denoise_variance_device spatial only and with mixed-batch moments,
+rt_denoise_given_variance_device) on seeded inputs of its own and saves every
+image and variance plane to one .npz; --compare takes those too.
+
+    RTX_LIB=... python tools/frame_dump.py --display --out a.npz"""
 import argparse
 import os
 import sys
@@ -16,6 +23,89 @@ sys.path.insert(0, os.path.join(ROOT, "real-time-ray-tracing-engine_amd"))
 sys.path.insert(0, ROOT)
 
 
+def same_bits(x, y):
+    return x.shape == y.shape and np.array_equal(x.view(np.uint64), y.view(np.uint64))
+
+
+def compare(pa, pb):
+    """Bit for bit: two .npy arrays, or every array of two .npz files."""
+    x, y = np.load(pa), np.load(pb)
+    if not pa.endswith(".npz"):
+        same = same_bits(x, y)
+        diff = 0 if same else int(np.count_nonzero(x.view(np.uint64) != y.view(np.uint64)))
+        print({"bit_identical": bool(same), "differing_doubles": diff, "shape": list(x.shape),
+               "max_abs_diff": float(np.nanmax(np.abs(x - y))) if x.shape == y.shape else None})
+        return same
+    differing = sorted(k for k in set(x.files) | set(y.files)
+                       if k not in x.files or k not in y.files or not same_bits(x[k], y[k]))
+    print({"bit_identical": not differing, "arrays": len(x.files), "doubles": int(sum(x[k].size for k in x.files)),
+           "differing_arrays": differing})
+    return not differing
+
+
+W, H, G, BATCH = 70, 33, 16, 2  # ragged 8x8 tiles, a partial 64-wide block
+
+
+def display_inputs(seed):
+    """(rgb sums, guide sums, mixed tile strata with 0s, s1, s2, a variance plane), non-finite entries included."""
+    rng = np.random.default_rng(seed)
+    rgb = rng.uniform(0.0, 2.0, (H, W, 3)) * G
+    rgb[20, 30, 1] = np.nan
+    rgb[28, 5, 0] = np.inf
+    rgb[2:11, 50:59] = np.nan
+    left = np.arange(W)[None, :, None] < W // 2  # an edge in the normals
+    n = rng.normal(size=(H, W, 3)) * 0.05 + np.where(left, (0.0, 0.0, 1.0), (1.0, 0.0, 0.0))
+    hits = np.full((H, W), float(G))
+    hits[:H // 4, :W // 5] = 0.0
+    hits[H // 4, :W // 5] = G / 2.0
+    alb = rng.uniform(0.2, 0.9, (H, W, 3))
+    alb[3:6, 40:44] = 0.001
+    guides = np.zeros((H, W, 8))
+    guides[..., 0:3] = np.where(hits[..., None] > 0, alb, 1.0) * G
+    guides[..., 3:6] = n / np.linalg.norm(n, axis=-1, keepdims=True) * hits[..., None]
+    guides[..., 6] = (5.0 + 0.02 * np.arange(W)[None, :] + 0.3 * (np.arange(H)[:, None] > H // 2)) * hits
+    guides[..., 7] = hits
+    tx, ty = (W + 7) // 8, (H + 7) // 8
+    strata = ((np.arange(tx * ty) * 5) % 13).astype(np.int32)
+    s1 = rng.uniform(0.5, 1.5, (H, W)) * np.repeat(np.repeat((strata // BATCH).reshape(ty, tx), 8, 0), 8, 1)[:H, :W]
+    s2 = s1 * s1 * rng.uniform(0.3, 0.6, (H, W))
+    s1[20, 31] = s2[12, 5] = np.nan
+    var = rng.uniform(0.0, 0.05, (H, W))
+    var[4, 4], var[5, 6], var[7, 60] = np.nan, -1.0, np.inf
+    return rgb, guides, strata, s1, s2, var
+
+
+def display(a):
+    import torch
+    from rtx import abi
+    from rtx.denoise import HipOps
+    f = abi.Frame()
+    f.image_width, f.image_height, f.sqrt_spp, f.max_depth, f.pixel_samples_scale = W, H, 2, 8, 0.25
+    ops = HipOps(torch.device("cuda", 0), torch.cuda.current_stream())
+    rgb, guides, strata, s1, s2, var = (torch.from_numpy(x).cuda() for x in display_inputs(a.seed))
+    off = dict(sigma_normal=-1, sigma_depth=-1, sigma_hit=-1)
+    cases = [("passes %d" % p, dict(passes=p)) for p in (-1, 1, 5, 8)] + [("sigmas off", dict(off, passes=5))]
+    out = {}
+    for label, params in cases:
+        plain = dict(params, sigma_color=-1) if label == "sigmas off" else params
+        guided = dict(params, sigma_lum=-1) if label == "sigmas off" else params
+        out["plain, " + label] = ops.denoise(f, rgb, 1.0 / G, None, guides, G, plain)
+        out["plain tiles, " + label] = ops.denoise(f, rgb, 1.0, strata, guides, G, plain)
+        for name, call in (
+                ("spatial", lambda v: ops.denoise_variance(f, rgb, 1.0 / G, None, guides, G, params=guided,
+                                                           variance_out=v)),
+                ("moments", lambda v: ops.denoise_variance(f, rgb, 1.0, strata, guides, G, s1, s2, BATCH, guided,
+                                                           variance_out=v)),
+                ("given", lambda v: ops.denoise_given_variance(f, rgb, 1.0 / G, None, guides, G, var, guided,
+                                                               variance_out=v))):
+            v = torch.zeros((H, W), dtype=torch.float64, device="cuda")
+            out["%s, %s" % (name, label)] = call(v)
+            out["%s variance, %s" % (name, label)] = v
+    torch.cuda.synchronize()
+    np.savez(a.out, **{k: t.cpu().numpy() for k, t in out.items()})
+    print({"display": True, "arrays": len(out), "out": a.out})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="C4")
@@ -24,14 +114,12 @@ def main():
     ap.add_argument("--seed", type=int, default=7)
     ap.add_argument("--out", default="")
     ap.add_argument("--compare", nargs=2, default=None)
+    ap.add_argument("--display", action="store_true")
     a = ap.parse_args()
     if a.compare:
-        x, y = (np.load(p) for p in a.compare)
-        same = x.shape == y.shape and np.array_equal(x.view(np.uint64), y.view(np.uint64))
-        diff = 0 if same else int(np.count_nonzero(x.view(np.uint64) != y.view(np.uint64)))
-        print({"bit_identical": bool(same), "differing_doubles": diff, "shape": list(x.shape),
-               "max_abs_diff": float(np.nanmax(np.abs(x - y))) if x.shape == y.shape else None})
-        sys.exit(0 if same else 1)
+        sys.exit(0 if compare(*a.compare) else 1)
+    if a.display:
+        return display(a)
     import torch  # noqa: F401  (the library shares torch's HIP runtime)
     from rtx import abi
     from rtx.render import Renderer, camera_frame
