@@ -69,12 +69,12 @@ struct KArgs {
 // here instead of silently shifting what the persistent instance reads (its
 // frames are also checked bit for bit against the one-unit-per-wave instance
 // on the GPU: tests/test_persistent.py, and through every BASELINE band).
-static_assert(sizeof(DScene) == 160 && alignof(DScene) == 8, "DScene kernarg layout");
+static_assert(sizeof(DScene) == 176 && alignof(DScene) == 8, "DScene kernarg layout");
 static_assert(sizeof(DCamera) == 208 && alignof(DCamera) == 8, "DCamera kernarg layout");
 static_assert(sizeof(DLaunch) == 112 && alignof(DLaunch) == 8, "DLaunch kernarg layout");
-static_assert(offsetof(KArgs, S) == 0 && offsetof(KArgs, C) == 160 && offsetof(KArgs, P) == 368 &&
-                  offsetof(KArgs, out) == 480 && offsetof(KArgs, stats) == 488 &&
-                  sizeof(KArgs) == 496,
+static_assert(offsetof(KArgs, S) == 0 && offsetof(KArgs, C) == 176 && offsetof(KArgs, P) == 384 &&
+                  offsetof(KArgs, out) == 496 && offsetof(KArgs, stats) == 504 &&
+                  sizeof(KArgs) == 512,
               "KArgs must mirror render_tiles' kernarg layout");
 static_assert(offsetof(DLaunch, n_chunks) == 56 && offsetof(DLaunch, unit_ctr) == 64 &&
                   offsetof(DLaunch, grid_cap) == 72 && offsetof(DLaunch, n_head) == 76 &&

@@ -63,6 +63,25 @@ struct DSphere {     // 64 B — Sphere.hpp: m_center Ray (c0, c1-c0), m_radius
   double rr;         // r*r, as Sphere::hit computes it
 };
 
+// One root item of a flat world of static, untransformed spheres (DScene::roots,
+// in root-item order): what the plain flat instance reads of items[i] and
+// spheres[items[i].idx], copied into one record whose address depends on
+// nothing loaded.  The test half is one 8-dword load for the walk; the record
+// half joins it for the winning item only (rt_path.h trace, trace_tail).
+struct DRootTest {   // 32 B — Sphere::hit's operands
+  double c0[3];
+  double rr;
+};
+struct DRoot {       // 48 B
+  DRootTest test;
+  double inv_r;      // DSphere::inv_r
+  int32_t mat;       // DItem::mat
+  int32_t pad;
+};
+static_assert(sizeof(DRootTest) == 32 && sizeof(DRoot) == 48, "DRoot layout");
+// (the material folded in as well -- kind, solid colour, metal and dielectric
+// constants, 88 B: C2 no faster, profiles/flat_table_material_variant.patch)
+
 struct DQuad {       // 144 B — Plane.hpp members
   double Q[3], u[3], v[3];
   double n[3];       // unit normal
@@ -193,6 +212,7 @@ struct DScene {      // kernel argument (by value)
   const DTex *texs;
   const DPerlin *perlin;
   const DLight *lights;
+  const DRoot *roots;    // packed root-item table of a flat static all-sphere world (n_roots records)
   int32_t n_lights;
   int32_t n_nodes;
   int32_t root_is_leaf;  // whole world is one leaf: items [0, n_root_items)
@@ -209,6 +229,9 @@ struct DScene {      // kernel argument (by value)
                           // block per CU) or 4 (deep trees); 0: no persistent launches
   int32_t lds_perlin;     // 1: the scene's one Perlin table is staged in LDS by the noise
                           // instances' blocks (perlin_lds); 0: read from HBM
+  int32_t n_roots;        // records in roots: n_root_items, or 0 (no table: the world is not flat, has
+                          // a quad, a moving sphere or a transform among its root items)
+  int32_t pad_;
 };
 
 // Scene features (kernel specialisation keys)

@@ -539,6 +539,9 @@ RT_HD RT_FI void sphere_record(const DSphere &s, const Ray &r, double t, int mat
 // ... in the plain flat instance (C2 +2.7 %); the rich flat instances have no
 // SGPRs to spare for the records (C4 -1.6 %; profiles/r03d_ab.log)
 #define RT_UNIFORM_LOADS_F(F) ((F) == F_FLAT)
+// The packed root table (DScene::roots) serves the plain flat instance's walk
+// and hit record; the rich flat instances keep the item walk, as above.
+#define RT_ROOT_TABLE_F(F) ((F) == F_FLAT)
 RT_HD RT_FI double comp(V3 v, int a) { return a == 0 ? v.x : (a == 1 ? v.y : v.z); } // no private array
 // SEL: the quad's axis components picked by value selects, not by an indexed
 // load -- for a record held in registers (a uniform scalar load, ldu), where
@@ -1422,6 +1425,16 @@ RT_HD RT_FI bool trace_tail(const DScene &S, const Ray &r, Hit &h, const Key &ke
     }
   };
   if (!best_full) {
+    if constexpr (RT_ROOT_TABLE_F(F)) {
+      if (S.n_roots) { // wave-uniform; the winner's DRoot in one load, not item -> sphere
+        const DRoot R = S.roots[best];
+        DSphere s; // c0 and inv_r are all the static record reads
+        s.c0[0] = R.test.c0[0], s.c0[1] = R.test.c0[1], s.c0[2] = R.test.c0[2];
+        s.inv_r = R.inv_r;
+        sphere_record<false>(s, r, closest, R.mat, h);
+        return true;
+      }
+    }
     if constexpr (kFlat) {
       if (S.static_spheres) { // wave-uniform: a scalar branch, as in the flat walk
         item_record(UTag<false>{});
@@ -1604,7 +1617,41 @@ RT_HD RT_FI bool trace(const DScene &S, const Ray &r, Hit &h, const Key &key,
     // A world without a moving sphere (DScene::static_spheres, wave-uniform)
     // runs its own instantiation of the loop: one scalar branch per segment,
     // outside the item loop, between two loops -- it stays a branch.
-    if (S.static_spheres) {
+    // A world with a root table (DScene::n_roots: static untransformed spheres
+    // only) runs a third one: each test reads the 32-B test half of its DRoot
+    // -- one scalar load whose address depends on nothing loaded, where the
+    // item walk loads the DItem, waits, and loads the DSphere at its idx -- and
+    // has no kind branch and no transform code.  sphere_root<false> sees the
+    // same c0 and rr in the same operand order: every t is the item walk's.
+    if (RT_ROOT_TABLE_F(F) && S.n_roots) {
+      const int n = S.n_roots;
+      auto load_test = [&](int ii) { return ldu<true>(&S.roots[ii].test, 0); };
+      auto test_root = [&](const DRootTest &e, int ii) {
+        if (STATS) {
+          cnt.wleaf += wave_once();
+          cnt.spheres++;
+        }
+        DSphere s; // c0 and rr are all the static root search reads
+        s.c0[0] = e.c0[0], s.c0[1] = e.c0[1], s.c0[2] = e.c0[2];
+        s.rr = e.rr;
+        double t;
+        if (sphere_root<false>(s, r, a, tmin, closest, t, true, ya)) {
+#if defined(__HIP_DEVICE_COMPILE__)
+          // keeps the update a branch taken by the lanes that hit, as in the
+          // item walk: folded into selects it costs every test five more VALU
+          // instructions (C2 SQ_INSTS_VALU +1.4 %, profiles/flat_table_blocks.md)
+          asm volatile("");
+#endif
+          closest = t;
+          if constexpr (kBoxes) cl32 = f32_up_c(closest);
+          best = ii;
+        }
+      };
+      // one load per test.  Entry ii + 1 loaded before entry ii is tested, or
+      // every entry of a world of at most 4 loaded before the first test: C2
+      // no faster (profiles/flat_table_one_ahead_variant.patch, _up_front_).
+      for (int ii = 0; ii < n; ++ii) test_root(load_test(ii), ii);
+    } else if (S.static_spheres) {
       for (int ii = 0; ii < S.n_root_items; ++ii) test_item_m(UTag<true>{}, UTag<false>{}, ii);
     } else {
       for (int ii = 0; ii < S.n_root_items; ++ii) test_item_m(UTag<true>{}, UTag<true>{}, ii);

@@ -1133,6 +1133,7 @@ int compile_scene(const rt_scene_desc *desc, HostScene &out, std::string &err) {
   }
   Compiler c(desc, out, err);
   if (!c.run()) return err.rfind("UNSUPPORTED", 0) == 0 ? RT_ERR_UNSUPPORTED : RT_ERR_INVALID;
+  build_root_table(out);
   return RT_OK;
 }
 

@@ -24,6 +24,7 @@ struct HostScene {
   std::vector<DTex> texs;
   std::vector<DPerlin> perlin;
   std::vector<DLight> lights;
+  std::vector<DRoot> roots;  // build_root_table: one per root item, or empty
   int32_t root_is_leaf = 0;
   int32_t n_root_items = 0;
   int32_t bvh_depth = 0;
@@ -49,6 +50,32 @@ inline int32_t all_spheres_static(const HostScene &H) {
   for (const DSphere &s : H.spheres)
     if (s.dir[0] != 0.0 || s.dir[1] != 0.0 || s.dir[2] != 0.0) return 0;
   return 1;
+}
+
+// The packed root-item table (DScene::roots; rt_layout.h DRoot): built for a
+// flat world whose root items are all untransformed spheres and in which no
+// sphere moves -- the world the static sphere-only walk of the plain flat
+// instance serves.  The values are copies of the doubles in DSphere and of
+// DItem::mat, in root-item order; nothing is recomputed.  Every other world
+// gets no table and keeps the item -> sphere walk.  Called once the host's
+// world tree is final (compile_scene); a device-built tree leaves it empty.
+inline void build_root_table(HostScene &H) {
+  H.roots.clear();
+  if (!H.root_is_leaf || H.n_root_items <= 0 || (size_t)H.n_root_items > H.items.size()) return;
+  if (!all_spheres_static(H)) return;
+  for (int32_t i = 0; i < H.n_root_items; ++i)
+    if (H.items[i].kind != I_SPHERE || H.items[i].xf_count != 0) return;
+  H.roots.resize(H.n_root_items);
+  for (int32_t i = 0; i < H.n_root_items; ++i) {
+    const DItem &it = H.items[i];
+    const DSphere &s = H.spheres[it.idx];
+    DRoot &r = H.roots[i];
+    for (int a = 0; a < 3; ++a) r.test.c0[a] = s.c0[a];
+    r.test.rr = s.rr;
+    r.inv_r = s.inv_r;
+    r.mat = it.mat;
+    r.pad = 0;
+  }
 }
 
 // The feature bits of the path-tracer instance a compiled scene needs
@@ -88,6 +115,7 @@ inline void for_each_table(F &&f) {
   f(&DScene::texs, &HostScene::texs);
   f(&DScene::perlin, &HostScene::perlin);
   f(&DScene::lights, &HostScene::lights);
+  f(&DScene::roots, &HostScene::roots);
 }
 
 // What a DScene holds of a compiled scene beside its tables: the counts, the
@@ -100,6 +128,7 @@ inline void bind_counts(DScene &S, const HostScene &H) {
   S.root_is_leaf = H.root_is_leaf;
   S.n_root_items = H.n_root_items;
   S.static_spheres = all_spheres_static(H);
+  S.n_roots = (int32_t)H.roots.size();
   S.features = scene_features(H) | (H.root_is_leaf ? RT_FEAT_FLAT : 0);
 }
 
