@@ -360,7 +360,9 @@ typedef struct rt_scene_info {
   int32_t quad_bytes;   /* bytes per quad record */
   int64_t device_bytes; /* total device bytes of the scene */
   int32_t features;     /* kernel instance: bit0 media, bit1 transforms, bit2 lights, bit3 noise,
-                           bit4 flat world, bit5 4-wide BVH */
+                           bit4 flat world, bit5 4-wide BVH; bit6: every material is Lambertian
+                           with a solid colour (a world of bit4 alone then runs the
+                           Lambertian-only instance) */
   int32_t lds_nodes;    /* BVH nodes (BFS prefix) the kernel stages in LDS per block */
   int32_t bvh_builder;  /* the builder that made the world BVH: RT_BVH_HOST / RT_BVH_DEVICE /
                            RT_BVH_DEVICE_SAH */

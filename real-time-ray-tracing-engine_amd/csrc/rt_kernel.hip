@@ -175,7 +175,7 @@ __device__ __forceinline__ int order_tile(const DLaunch &L, int k) {
 // every launch beats the probe's (r06ad / r06af: 8-way C2 share).
 // rtk_cost_f mirrors it for the host.
 #define RT_COST_F(F) ((F) == F_FLAT)
-extern "C" int rtk_cost_f(int features) { return RT_COST_F((unsigned)features) ? 1 : 0; }
+extern "C" int rtk_cost_f(int features) { return RT_COST_F((unsigned)features & F_ALL) ? 1 : 0; }
 template <bool FRESH>
 __device__ __forceinline__ double *out_arg(double *out) {
   if constexpr (FRESH) {
@@ -219,7 +219,8 @@ extern "C" hipError_t rtk_unit_times_clear(void) {
 // PCW: 0 = one work unit per wavefront; else a persistent instance with
 // blocks of PCW waves (kPcWaves = one block per CU; kWaves when the traversal
 // stacks of 16 waves do not fit the CU's LDS, e.g. deep 4-wide trees)
-template <bool STATS, unsigned F, int PCW = 0, bool COST = false>
+// MS: the material set shade is compiled for (rt_path.h MatSet)
+template <bool STATS, unsigned F, int PCW = 0, bool COST = false, MatSet MS = M_ANY>
 __global__ __launch_bounds__(64 * (PCW ? PCW : block_waves(F))) __attribute__((amdgpu_waves_per_eu(RT_WAVES_PER_EU(F)))) void render_tiles(DScene S_, DCamera C, DLaunch P, double *out,
                                                     unsigned long long *stats) {
   constexpr bool PC = PCW > 0;
@@ -400,7 +401,7 @@ __global__ __launch_bounds__(64 * (PCW ? PCW : block_waves(F))) __attribute__((a
     if (ps.active) {
       if (STATS) n_segments++;
       const uint32_t nv0 = cnt.nodes;
-      bool cont = segment<STATS, F, PC>(
+      bool cont = segment<STATS, F, PC, MS>(
           S, C, ps, key, stk, lnodes, cnt, (RT_LDS LeafPool *)&leaf_pool[RT_LEAF_SHARE_F(F) ? wv : 0], lp);
       if (STATS) v_trace = cnt.nodes - nv0;
       if (!cont) {
@@ -532,6 +533,17 @@ const RenderFn *render_table(bool stats) {
   return stats ? counted.data() : plain.data();
 }
 
+// The one-unit render instance of a scene's DScene::features: the table's, or
+// for the plain flat world of a diffuse-only materials table (RT_FEAT_DIFFUSE)
+// its Lambertian-only twin -- one more kernel, keyed on the material set
+// (rt_path.h MatSet).  The STATS and COST instances, the rich flat worlds and
+// the BVH worlds have no twin and stay general.  C2: profiles/diffuse_ab.log.
+RenderFn render_instance(int features, bool stats) {
+  if (!stats && (features & RT_FEAT_DIFFUSE) && (unsigned)(features & F_ALL) == F_FLAT)
+    return render_tiles<false, F_FLAT, 0, false, M_DIFFUSE>;
+  return render_table(stats)[features & F_ALL];
+}
+
 } // namespace
 
 // ---------------------------------------------------------------- launchers
@@ -543,7 +555,7 @@ extern "C" hipError_t rtk_instance_attrs(int features, int pc_waves, KernelAttrs
   const unsigned f = (unsigned)(features & F_ALL);
   hipFuncAttributes a;
   hipError_t e = hipFuncGetAttributes(
-      &a, reinterpret_cast<const void *>(pc_waves ? persistent_instance(f, pc_waves) : render_table(false)[f]));
+      &a, reinterpret_cast<const void *>(pc_waves ? persistent_instance(f, pc_waves) : render_instance(features, false)));
   if (e != hipSuccess) return e;
   attrs->num_regs = a.numRegs;
   attrs->static_lds = (int32_t)a.sharedSizeBytes;
@@ -579,7 +591,7 @@ extern "C" hipError_t rtk_launch_render(const DScene *S, const DCamera *C, const
   const int bw = block_waves((unsigned)S->features);
   int blocks = (int)((units + bw - 1) / bw);
   if (blocks == 0) return hipSuccess;
-  RenderFn fn = render_table(stats != nullptr)[S->features & F_ALL];
+  RenderFn fn = render_instance(S->features, stats != nullptr);
   // a launch that measures its tiles' costs (rt_api.cpp: the first tile-subset
   // launch of a shape in the flat world)
   const bool cost = stats == nullptr && P->tile_cost != nullptr;

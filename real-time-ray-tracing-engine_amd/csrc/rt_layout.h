@@ -217,7 +217,8 @@ struct DScene {      // kernel argument (by value)
   int32_t n_nodes;
   int32_t root_is_leaf;  // whole world is one leaf: items [0, n_root_items)
   int32_t n_root_items;
-  int32_t features;      // RT_FEAT_* bits: selects the specialised kernel instance
+  int32_t features;      // RT_FEAT_* bits: selects the specialised kernel instance (bits 0-5: the
+                         // instance table's key; RT_FEAT_DIFFUSE above it)
   int32_t n_mitems;
   int32_t stack_depth;   // per-lane traversal stack entries (BVH depth + 1)
   int32_t n_lds_nodes;   // nodes [0, n_lds_nodes) are staged in LDS (BFS order: top levels)
@@ -241,6 +242,12 @@ struct DScene {      // kernel argument (by value)
 #define RT_FEAT_NOISE 8  // Perlin noise textures
 #define RT_FEAT_FLAT 16  // flat world (root_is_leaf): no BVH walk
 #define RT_FEAT_BVH4 32  // the world BVH is 4-wide (DNode4); never with RT_FEAT_FLAT
+// Above the instance-table key (bits 0-5): a property of the materials table.
+// Every material is Lambertian with a solid-colour texture (rt_scene.h
+// diffuse_only): the plain flat world (RT_FEAT_FLAT alone) then runs the
+// Lambertian-only instance (rt_path.h MatSet, rt_kernel.hip); every other
+// world ignores the bit.
+#define RT_FEAT_DIFFUSE 64
 // bytes per BVH node staged in LDS (DNode4 / DNodeL / DNode)
 #define RT_LDS_NODE_BYTES(features)                                                                \
   (((features) & RT_FEAT_BVH4) ? (int)sizeof(DNode4) : (int)sizeof(DNodeL))

@@ -91,13 +91,109 @@ RT_HD RT_FI double rcp_n(double x) {
   return 1.0 / x;
 #endif
 }
-RT_HD RT_FI V3 unitv(V3 a) { // Vec3::normalize (Vec3.hpp:150-158)
+// Vec3::normalize (Vec3.hpp:150-158) as a root and a reciprocal, each from its
+// own transcendental: what unitv runs, and the reference that
+// tests/test_unitv_fused.py holds the one-transcendental variant below against.
+RT_HD RT_FI V3 unitv_2t(V3 a) {
   double l = sqrt_n(len2(a)); // l <= 1e-8 (incl. every input below 2^-767) -> (1, 0, 0)
   if (l > 1e-8) {
     double s = rcp_n(l); // l in (1e-8, 2^512] or +inf
     return v3(a.x * s, a.y * s, a.z * s);
   }
   return v3(1.0, 0.0, 0.0);
+}
+// A measured variant, not the product build (RT_UNITV_FUSED, below): C2's
+// Lambertian-only instance 1.3 % faster in every interleaved round but with
+// ranges that touch, C3 and C5 1.2 % slower (profiles/unitv_fused_ab.log,
+// DESIGN.md §9).  Kept buildable and checked, like RT_LEAF_SHARE.
+// l = sqrt_n(x) and RN(1/l) from the one v_rsq_f64 that sqrt_n issues: rcp_n's
+// v_rcp_f64 seed and its first Newton step are replaced by what the root's own
+// iteration leaves behind.  For l in (1e-8, 2^512]:
+//  * seed.  After sqrt_n's Goldschmidt step, h = 1/(2 sqrt(x)) (1 + eps) with
+//    |eps| of the order of the square of v_rsq_f64's error, far below the
+//    2^-26 that the rest needs; the root's two corrections move g, not h, and
+//    l = RN(sqrt(x)) differs from sqrt(x) by at most 2^-53 relative.  So
+//    y1 = h + h (exact) is 1/l to well within 2^-26.
+//  * one Newton step.  e = 1 - l y1 is exact in the FMA up to its one
+//    rounding, y2 = y1 + y1 e has relative error e^2 + 2^-53: y2 is 1/l to
+//    within one ulp, which is all the correction asks of it.
+//  * Markstein's correction (div_mk's references).  r = 1 - l y2 is exact (one
+//    FMA, |r| < 2^-51), and q = y2 + r y2 rounds to RN(1/l) -- rcp_n's own
+//    last two operations on an operand of the same quality.
+//  * the exception.  For l with an all-ones significand, 1/l lies just above
+//    a power of two, by a little more than half an ulp of that binade, and y2
+//    can be that power of two.  Then l y2 = 1 - 2^-53, r = 2^-53 exactly, and
+//    y2 + r y2 is an exact tie that rounds to even, to y2, one ulp below
+//    RN(1/l).  r is nudged up by one ulp there: the sum then lies above the
+//    tie and rounds to y2 + ulp.  Harmless elsewhere: r == 2^-53 means
+//    l y2 = 1 - 2^-53 whatever y2 is, and for a y2 = m 2^k with m in (1, 2)
+//    r y2 is (m / 2) ulp(y2), between a half and one ulp before and after
+//    the nudge, so the sum rounds to the same neighbour.
+// x = +-0 / +inf / NaN / x < 0: l as sqrt_n gives it; 1/+inf = +0 as in rcp_n;
+// the other three never reach the reciprocal (unitv's l > 1e-8 test).
+// Host check with perturbed seeds, and that the nudge is needed:
+// tests/native/rt_unitv_check.cpp; on gfx950 with the real seed,
+// against sqrt_n then rcp_n: tests/test_unitv_fused.py.
+RT_HD RT_FI double rcp_from_h(double l, double h) {
+  const double y1 = h + h;
+  const double e = fma(-l, y1, 1.0);
+  const double y2 = fma(y1, e, y1);
+  double r = fma(-l, y2, 1.0);
+  if (r == 0x1p-53) r = 0x1.0000000000001p-53; // the all-ones tie
+  return fma(r, y2, y2);
+}
+// sqrt_n's iteration from its seed y = v_rsq_f64(x), before the class fixup; h
+// as the Goldschmidt step leaves it (host: the check above feeds it seeds)
+RT_HD RT_FI double sqrt_rsq(double x, double y, double &h) {
+  double g = x * y;
+  h = 0.5 * y;
+  const double r = fma(-h, g, 0.5);
+  g = fma(g, r, g);
+  h = fma(h, r, h);
+  double d = fma(-g, g, x);
+  g = fma(d, h, g);
+  d = fma(-g, g, x);
+  g = fma(d, h, g);
+  return g;
+}
+#ifndef RT_UNITV_FUSED
+#define RT_UNITV_FUSED 0 // A/B builds: make EXTRA=-DRT_UNITV_FUSED=1 runs the one-transcendental form on the device
+#endif
+// sqrt_n(x), leaving h; and rcp_n(l) of that root from that h: on the device the
+// class selects of sqrt_n and rcp_n around sqrt_rsq and rcp_from_h (the host
+// forms only keep a host pass compiling: unitv's host form is unitv_2t)
+RT_HD RT_FI double sqrt_h(double x, double &h) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const double g = sqrt_rsq(x, __builtin_amdgcn_rsq(x), h);
+  return __builtin_isfpclass(x, 0x260) ? x : g; // +-0, +inf: x itself
+#else
+  h = 0.5 / sqrt(x);
+  return sqrt(x);
+#endif
+}
+RT_HD RT_FI double rcp_h(double l, double h) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const double q = rcp_from_h(l, h);
+  return __builtin_isfpclass(l, 0x200) ? 0.0 : q; // 1/+inf = +0
+#else
+  return 1.0 / l;
+#endif
+}
+RT_HD RT_FI V3 unitv_fused(V3 a) {
+  double h;
+  double l = sqrt_h(len2(a), h); // l <= 1e-8 (incl. every input below 2^-767) -> (1, 0, 0)
+  if (l > 1e-8) {
+    double s = rcp_h(l, h); // l in (1e-8, 2^512] or +inf
+    return v3(a.x * s, a.y * s, a.z * s);
+  }
+  return v3(1.0, 0.0, 0.0);
+}
+RT_HD RT_FI V3 unitv(V3 a) { // Vec3::normalize (Vec3.hpp:150-158)
+#if defined(__HIP_DEVICE_COMPILE__) && RT_UNITV_FUSED
+  return unitv_fused(a);
+#else
+  return unitv_2t(a);
+#endif
 }
 
 struct Ray {
@@ -287,6 +383,15 @@ enum : unsigned {
   F_BVH4 = 32u,  // 4-wide world BVH (DNode4); never with F_FLAT
   F_ALL = 63u
 };
+// The material set an instance is compiled for (shade, tex_value): a key beside
+// the feature set, from the scene's materials table (rt_scene.h diffuse_only,
+// RT_FEAT_DIFFUSE).  M_DIFFUSE: every material is Lambertian with a solid
+// colour, so shade is its Lambertian code alone -- the same operations on the
+// same operands in the same order as the general form runs for such a hit,
+// without the kind compares, the branches' merged results and the registers the
+// other materials' code holds.  Only the plain flat instance has a diffuse
+// twin (rt_kernel.hip).
+enum MatSet : unsigned { M_ANY = 0u, M_DIFFUSE = 1u };
 
 // ---------------------------------------------------------------- textures
 // sin(x) for NoiseTexture::value (NoiseTexture.cpp:33), within 1 ulp (checked
@@ -412,8 +517,9 @@ __device__ __forceinline__ const RT_LDS PerlinLds *perlin_lds() {
 // (profiles/r03s_ab.log).  fp32 octaves on an fp32 gradient copy: C4 +0.25 %,
 // within noise (r03r_ab.log), so the reference's fp64 arithmetic is kept.
 
-template <unsigned F>
+template <unsigned F, MatSet MS = M_ANY>
 RT_HD V3 tex_value(const DScene &S, int t, V3 p) {
+  if constexpr (MS == M_DIFFUSE) return ld3(S.texs[t].color); // every texture in use is solid
   for (int guard = 0; guard < 64; ++guard) {
     const DTex &T = S.texs[t];
     if (T.kind == RT_TEX_SOLID) return ld3(T.color);
@@ -1992,17 +2098,23 @@ RT_HD RT_FI bool advance(PathState &ps, const DCamera &C) {
 // pure overhead) -2 %, C4 -1 % (more spills): merged in the plain BVH instances only.
 // Re-measured on the round-6 build (profiles/r06am_*): C2 -2.9 %, C4 -2.4 %.
 #define RT_SHADE_MERGE_F(F) (((F) & ~F_BVH4) == 0)
-template <bool STATS, unsigned F>
+template <bool STATS, unsigned F, MatSet MS = M_ANY>
 RT_HD RT_FI bool shade(const DScene &S, const DCamera &C, PathState &ps, const Key &key,
                        const Hit &h, Counters &cnt) {
   const uint32_t b = ps.bounce;
   const DMat M = S.mats[h.mat];
+  // kDiff: every material is Lambertian (MatSet): the other materials' branches
+  // are not compiled and `lamb` is a constant.  Only the plain flat instance has
+  // this form: there the merged prelude (kMerge) and the noise count, which read
+  // kinds without regard to MS, are not compiled either, so no kind is read.
+  constexpr bool kDiff = MS == M_DIFFUSE;
+  static_assert(MS == M_ANY || F == F_FLAT, "M_DIFFUSE is written for the plain flat instance only");
   if (STATS) cnt.shade++;
-  if (M.kind == RT_MAT_DIFFUSE_LIGHT) { // emits on the front face, never scatters
+  if (!kDiff && M.kind == RT_MAT_DIFFUSE_LIGHT) { // emits on the front face, never scatters
     if (STATS) cnt.wshade += wave_once();
     // Always add T * emitted (0 on the back face): a NaN/inf throughput must
     // poison the sample as the reference recursion does (NaN * 0 = NaN).
-    V3 e = h.front ? tex_value<F>(S, M.tex, h.p) : v3(0.0, 0.0, 0.0);
+    V3 e = h.front ? tex_value<F, MS>(S, M.tex, h.p) : v3(0.0, 0.0, 0.0);
     ps.T = ps.T * e;
     return false;
   }
@@ -2032,7 +2144,7 @@ RT_HD RT_FI bool shade(const DScene &S, const DCamera &C, PathState &ps, const K
     if (diel) ct1 = fmin(dot(-u1, h.n), 1.0);
     s1 = sqrt_n(lamb ? d1 : (diel ? 1.0 - ct1 * ct1 : fmax(0.0, 1.0 - z1 * z1)));
   }
-  if (kMerge && M.kind == RT_MAT_METAL) {
+  if (!kDiff && kMerge && M.kind == RT_MAT_METAL) {
     if (STATS) cnt.wshade += wave_once();
     V3 uv = v3(s1 * cp1, s1 * sp1, z1);
     V3 refl = u1 + (M.fuzz * uv);
@@ -2040,7 +2152,7 @@ RT_HD RT_FI bool shade(const DScene &S, const DCamera &C, PathState &ps, const K
     ps.ray = Ray{h.p, refl, r.tm};
     return advance(ps, C);
   }
-  if (kMerge && M.kind == RT_MAT_DIELECTRIC) {
+  if (!kDiff && kMerge && M.kind == RT_MAT_DIELECTRIC) {
     if (STATS) cnt.wshade += wave_once();
     double ri = h.front ? M.inv_ior : M.ior;
     const V3 ud = u1;
@@ -2064,7 +2176,7 @@ RT_HD RT_FI bool shade(const DScene &S, const DCamera &C, PathState &ps, const K
     ps.ray = Ray{h.p, dir, r.tm};
     return advance(ps, C);
   }
-  if (!kMerge && M.kind == RT_MAT_METAL) { // MetalMaterial.cpp:43-62
+  if (!kDiff && !kMerge && M.kind == RT_MAT_METAL) { // MetalMaterial.cpp:43-62
     if (STATS) cnt.wshade += wave_once();
     V3 refl = r.d - (2 * dot(r.d, h.n)) * h.n;
     double z = 1.0 - 2.0 * d0;
@@ -2077,7 +2189,7 @@ RT_HD RT_FI bool shade(const DScene &S, const DCamera &C, PathState &ps, const K
     ps.ray = Ray{h.p, refl, r.tm};
     return advance(ps, C);
   }
-  if (!kMerge && M.kind == RT_MAT_DIELECTRIC) { // DielectricMaterial.cpp:58-85
+  if (!kDiff && !kMerge && M.kind == RT_MAT_DIELECTRIC) { // DielectricMaterial.cpp:58-85
     if (STATS) cnt.wshade += wave_once();
     double ri = h.front ? M.inv_ior : M.ior; // 1/ior formed on the host
     V3 ud = unitv(r.d);
@@ -2103,7 +2215,7 @@ RT_HD RT_FI bool shade(const DScene &S, const DCamera &C, PathState &ps, const K
     return advance(ps, C);
   }
   // Lambertian (CosinePDF) or Isotropic (SpherePDF), mixed 50/50 with the lights
-  const bool lamb = (M.kind == RT_MAT_LAMBERTIAN);
+  const bool lamb = kDiff || (M.kind == RT_MAT_LAMBERTIAN);
   if (STATS) cnt.wshade += wave_once();
   // albedo: fetched early when a noise texture may run (its long evaluation
   // overlaps less live state there), late otherwise (shorter live range)
@@ -2113,7 +2225,7 @@ RT_HD RT_FI bool shade(const DScene &S, const DCamera &C, PathState &ps, const K
       cnt.noise++;
       cnt.wnoise += wave_once();
     }
-    att = tex_value<F>(S, M.tex, h.p);
+    att = tex_value<F, MS>(S, M.tex, h.p);
   }
   V3 w = kMerge ? u1 : unitv(h.n); // ONB(n), ONB.hpp:25-37
   V3 a = (fabs(w.x) > 0.9) ? v3(0, 1, 0) : v3(1, 0, 0);
@@ -2202,14 +2314,14 @@ RT_HD RT_FI bool shade(const DScene &S, const DCamera &C, PathState &ps, const K
     ps.T = ps.T * v3(0.0, 0.0, 0.0);             // (keeps an earlier NaN/inf alive)
     return false;
   }
-  if constexpr ((F & F_NOISE) == 0) att = tex_value<F>(S, M.tex, h.p);
+  if constexpr ((F & F_NOISE) == 0) att = tex_value<F, MS>(S, M.tex, h.p);
   V3 wgt = (1 / pdf) * (spdf * att);
   ps.T = ps.T * wgt;
   ps.ray = Ray{h.p, gd, r.tm};
   return advance(ps, C);
 }
 
-template <bool STATS, unsigned F, bool LP = false>
+template <bool STATS, unsigned F, bool LP = false, MatSet MS = M_ANY>
 RT_HD RT_FI bool segment(const DScene &S, const DCamera &C, PathState &ps,
                                         const Key &key, int *stk, const RT_LDS DNode *lnodes,
                                         Counters &cnt, RT_LDS LeafPool *pool = nullptr,
@@ -2223,7 +2335,7 @@ RT_HD RT_FI bool segment(const DScene &S, const DCamera &C, PathState &ps,
     ps.T = ps.T * ld3(C.bg); // miss -> background (Camera.cpp:242-243)
     return false;
   }
-  const bool cont = shade<STATS, F>(S, C, ps, key, h, cnt);
+  const bool cont = shade<STATS, F, MS>(S, C, ps, key, h, cnt);
   if (STATS && wave_once()) cnt.cshade += clk() - t1;
   return cont;
 }

@@ -97,6 +97,21 @@ inline int32_t scene_features(const HostScene &H) {
   return f;
 }
 
+// 1 when every entry of the materials table is Lambertian and the texture it
+// names is a solid colour (RT_FEAT_DIFFUSE): shade then needs no material kind
+// and tex_value is one colour load (rt_path.h M_DIFFUSE).  Over the table, not
+// over what the world references: an unused metal material turns it off, so
+// the bit never depends on reachability.  An empty table has no material to
+// vouch for.
+inline int32_t diffuse_only(const HostScene &H) {
+  if (H.mats.empty()) return 0;
+  for (const DMat &m : H.mats) {
+    if (m.kind != RT_MAT_LAMBERTIAN) return 0;
+    if (m.tex < 0 || (size_t)m.tex >= H.texs.size() || H.texs[m.tex].kind != RT_TEX_SOLID) return 0;
+  }
+  return 1;
+}
+
 // The scene's tables, named once: f(DScene member, HostScene vector) for each,
 // in the order the GPU library lays them out in a scene's device block
 // (rt_api.cpp).  A table added to DScene is added here and nowhere else.
@@ -129,7 +144,7 @@ inline void bind_counts(DScene &S, const HostScene &H) {
   S.n_root_items = H.n_root_items;
   S.static_spheres = all_spheres_static(H);
   S.n_roots = (int32_t)H.roots.size();
-  S.features = scene_features(H) | (H.root_is_leaf ? RT_FEAT_FLAT : 0);
+  S.features = scene_features(H) | (H.root_is_leaf ? RT_FEAT_FLAT : 0) | (diffuse_only(H) ? RT_FEAT_DIFFUSE : 0);
 }
 
 // The host binder: a DScene over the HostScene's own vectors (the CPU

@@ -68,6 +68,7 @@ class SceneDesc(C.Structure):
 RT_BVH_AUTO, RT_BVH_HOST, RT_BVH_DEVICE, RT_BVH_DEVICE_SAH = 0, 1, 2, 3
 # kernel instance bits (rt_scene_info.features)
 RT_FEAT_MEDIA, RT_FEAT_XFORM, RT_FEAT_LIGHTS, RT_FEAT_NOISE, RT_FEAT_FLAT, RT_FEAT_BVH4 = 1, 2, 4, 8, 16, 32
+RT_FEAT_DIFFUSE = 64  # above the instance key: every material is Lambertian with a solid colour
 
 
 class CameraDesc(C.Structure):

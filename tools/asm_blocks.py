@@ -1,17 +1,19 @@
 #!/usr/bin/env python3
 """Basic blocks of one render_tiles<STATS, F> instance in the gfx950 asm
 (make asm): instruction counts by class for the blocks that look like the BVH
-walk (fp32 FMAs / LDS reads).   python tools/asm_blocks.py F [--pc (the 16-wave persistent instance)] [--all] [--dump BB]"""
+walk (fp32 FMAs / LDS reads).   python tools/asm_blocks.py F [--pc (the 16-wave persistent instance)]
+[--diffuse (the Lambertian-only twin, rt_path.h M_DIFFUSE)] [--all] [--dump BB]"""
 import re
 import sys
 
 ASM = __import__("os").environ.get("ASM", "real-time-ray-tracing-engine_amd/build/asm/rt_kernel-hip-amdgcn-amd-amdhsa-gfx950.s")
 
 
-def blocks(F, stats=0, pc=0, cost=0):
+def blocks(F, stats=0, pc=0, cost=0, ms=0):
     s = open(ASM).read()
-    # render_tiles<STATS, F, PCW, COST> (COST: the flat world's cost-measuring instance)
-    name = "_ZN12_GLOBAL__N_112render_tilesILb%dELj%dELi%dELb%dEEEv6DScene7DCamera7DLaunchPdPy" % (stats, F, pc, cost)
+    # render_tiles<STATS, F, PCW, COST, MS> (COST: the flat world's cost-measuring instance; MS: the material set)
+    name = "_ZN12_GLOBAL__N_112render_tilesILb%dELj%dELi%dELb%dELN3rtp6MatSetE%dEEEv6DScene7DCamera7DLaunchPdPy" % (
+        stats, F, pc, cost, ms)
     i = s.index(name + ":")
     j = s.index(".Lfunc_end", i)
     out, cur = [], ["entry", []]
@@ -40,7 +42,7 @@ def classify(ins):
 
 if __name__ == "__main__":
     F = int(sys.argv[1])
-    bl = blocks(F, pc=16 if "--pc" in sys.argv else 0)
+    bl = blocks(F, pc=16 if "--pc" in sys.argv else 0, ms=1 if "--diffuse" in sys.argv else 0)
     if "--dump" in sys.argv:
         want = sys.argv[sys.argv.index("--dump") + 1]
         for b, ins in bl:

@@ -16,7 +16,8 @@ def functions(path):
     for line in open(path):
         m = re.match(r"(\S*render_tiles\S*):", line)
         if m and name is None:
-            name, body = m.group(1), []
+            # the default material set (rt_path.h M_ANY) names the instance builds before MatSet knew
+            name, body = m.group(1).replace("LN3rtp6MatSetE0E", ""), []
         elif name is not None:
             if line.startswith(".Lfunc_end"):
                 out[name], name = body, None

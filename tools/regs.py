@@ -27,9 +27,10 @@ if sys.argv[1:2] == ["--kernel"]:
     sys.exit(0)
 want = set(int(a) for a in sys.argv[1:])
 for k, v in rows.items():
-    m = re.search(r"render_tilesILb(\d)ELj(\d+)ELi(\d+)ELb(\d)E", k)
+    # ... and the material set (rt_path.h MatSet: 0 any, 1 diffuse)
+    m = re.search(r"render_tilesILb(\d)ELj(\d+)ELi(\d+)ELb(\d)E(?:LN3rtp6MatSetE(\d+)E)?", k)
     if not m or (want and int(m.group(2)) not in want):
         continue
-    print("STATS=%s F=%-2s PC=%-2s COST=%s VGPR %3s SGPR %3s spillV %3s spillS %3s occ %s scratch %s" % (
-        m.group(1), m.group(2), m.group(3), m.group(4), v.get("VGPRs"), v.get("SGPRs"), v.get("VGPRs Spill"),
+    print("STATS=%s F=%-2s PC=%-2s COST=%s MS=%s VGPR %3s SGPR %3s spillV %3s spillS %3s occ %s scratch %s" % (
+        m.group(1), m.group(2), m.group(3), m.group(4), m.group(5) or "0", v.get("VGPRs"), v.get("SGPRs"), v.get("VGPRs Spill"),
         v.get("SGPRs Spill"), v.get("Occupancy [waves/SIMD]"), v.get("ScratchSize [bytes/lane]")))
