@@ -4,9 +4,17 @@
 // The reference builds a binned-SAH tree on the CPU (BVHNode.cpp:21-123,
 // 168-254: 15 candidate planes x 3 axes, leaves <= 4); rt_scene.cpp's host
 // builder keeps its rules (16 bins per axis, leaves of <= 2 items, or <= 4 when a
-// split does not pay under unit traversal/intersection costs, balanced splits
-// near the traversal-stack depth budget).  This builder applies the same rules
-// top-down, one tree LEVEL per pair of launches, one wavefront per node:
+// split does not pay under unit traversal/intersection costs).  Near the
+// traversal-stack depth budget the host splits at the count median; this
+// builder splits there at the BIN BOUNDARY nearest the count median (longest
+// centroid axis), which halves a uniform cloud but bounds no tree's depth: a
+// skewed range keeps nearly every item in one bin and peels off the rest level
+// by level.  What keeps a tree inside the stack is the library's fallback to
+// the host build once the reported depth exceeds it (rt_api.cpp
+// build_world_tree; tests/test_device_bvh.py), and the reported depth is
+// checked against the tree itself (tests/test_bvh_builders_gpu.py).  This
+// builder applies the rules top-down, one tree LEVEL per pair of launches, one
+// wavefront per node:
 //
 //   sah_decide (wave per node of the level)
 //     pass 1: the node's box and centroid bounds (lane-strided loads over the
@@ -18,7 +26,8 @@
 //     SAH:    lane a*16+k evaluates the split of axis a before bin k (45 valid
 //             candidates) from prefix/suffix unions; a wave arg-min picks the
 //             cheapest (ties: lower axis, then higher k -- the host's scan
-//             order); leaf / split / forced balanced split as the host decides.
+//             order); leaf / split as the host decides, or the forced split
+//             nearest the count median.
 //   exclusive scan (hipCUB) of the split flags: BFS index of each inner node
 //             and the slots of its two children in the next level;
 //   sah_apply (wave per node)
@@ -168,9 +177,10 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void sah_decide(
   const bool leaf = cnt <= kLeafMax || (nd.depth == 0 && cnt <= RT_FLAT_MAX);
   int need = 0;
   while ((1 << need) < cnt) ++need;
-  // depth budget (the host's force_median): near the traversal-stack limit
-  // split into count halves -- at the bin boundary of the longest centroid
-  // axis closest to the median, or by position when every centroid coincides
+  // depth budget (the host's force_median bound): near the traversal-stack
+  // limit split at the bin boundary of the longest centroid axis closest to
+  // the count median (count halves only where the bins allow), or by position
+  // when every centroid coincides
   const bool force = nd.depth + need >= stack_budget;
   if (!leaf) {
     // ---- pass 2: bins

@@ -2,8 +2,10 @@
 (rt_bvh_sah.hip) and the linear BVH (rt_bvh_build.hip) give the same images as
 the host SAH tree (the closest hit does not depend on the tree), match the
 oracle, the SAH tree's cost stays within a few percent of the host SAH tree's,
-balanced splits keep it inside the traversal stack, and a tree deeper than the
-stack falls back to the host build."""
+and a tree deeper than the stack (either builder's: near the depth budget the
+SAH builder splits at the bin boundary nearest the count median, which bounds
+the depth of no tree) falls back to the host build.  The trees themselves are
+read back and checked node by node in tests/test_bvh_builders_gpu.py."""
 import os
 
 import numpy as np
@@ -45,6 +47,31 @@ def test_device_bvh_matches_oracle_and_host_tree(name, w, spp):
         compare(out[b], out[abi.RT_BVH_HOST], 1e-12)
 
 
+def test_tiny_world_through_each_device_builder():
+    """three_spheres, 3 world items (<= RT_FLAT_MAX): the SAH builder's root is a
+    leaf of 3 -- a flat world, built on the device, so without the host's packed
+    root table -- and the linear BVH's two nodes make a world this small that is
+    NOT flat.  Either way the frame is the host tree's and the oracle's."""
+    S = load_scene(os.path.join(SCENES, "three_spheres.json"))
+    cam = S.camera_desc(image_width=64, samples_per_pixel=4, max_depth=8)
+    f = camera_frame(cam)
+    out, info = {}, {}
+    for b in (abi.RT_BVH_HOST,) + DEVICE:
+        S.bvh_builder = b
+        with Renderer(S) as R:
+            info[b] = R.info()
+            assert info[b]["bvh_builder"] == b and info[b]["n_objects"] == 3
+            out[b] = R.render(f, seed=9)
+    assert info[abi.RT_BVH_HOST]["features"] & abi.RT_FEAT_FLAT
+    sah, lbvh = info[abi.RT_BVH_DEVICE_SAH], info[abi.RT_BVH_DEVICE]
+    assert sah["features"] & abi.RT_FEAT_FLAT and sah["n_nodes"] == 0 and sah["bvh_depth"] == 0, sah
+    assert not lbvh["features"] & abi.RT_FEAT_FLAT and lbvh["n_nodes"] == 2 and lbvh["bvh_depth"] == 2, lbvh
+    ref = O.oracle_render(S, cam, O.MODE_COUNTER, 9)
+    for b in DEVICE:
+        compare(out[b], ref, 1e-4)
+        compare(out[b], out[abi.RT_BVH_HOST], 1e-12)
+
+
 def random_spheres(n, seed=1):
     rng = np.random.default_rng(seed)
     c = rng.uniform(-50, 50, size=(n, 3))
@@ -74,9 +101,11 @@ def test_auto_builder_uses_device_for_large_scenes():
     assert np.nanmean(dev) > 0
 
 
-def test_too_deep_device_tree_falls_back_to_host():
+@pytest.mark.parametrize("builder", DEVICE, ids=["RT_BVH_DEVICE", "RT_BVH_DEVICE_SAH"])
+def test_too_deep_device_tree_falls_back_to_host(builder):
+    """lbvh_max_depth bounds either device builder's tree (rt_api.cpp build_world_tree)."""
     S = load_scene(os.path.join(SCENES, "bouncing_seed42.json"))
-    S.bvh_builder = abi.RT_BVH_DEVICE
+    S.bvh_builder = builder
     cam = S.camera_desc(image_width=32, samples_per_pixel=4, max_depth=8)
     with Renderer(S, tuning={"lbvh_max_depth": 1}) as R:
         assert R.info()["bvh_builder"] == abi.RT_BVH_HOST
@@ -108,8 +137,8 @@ def test_device_sah_tree_quality_and_images():
 
 def test_device_sah_depth_budget_balanced_splits():
     """With the stack budget lowered to 8 levels, the device SAH builder switches
-    to balanced (count-median) splits below it: the tree stays shallow and the
-    image is unchanged."""
+    below it to the bin boundary nearest the count median: on this uniform cloud
+    the tree stays shallow, and the image is unchanged."""
     S = load_scene(random_spheres(20000, seed=5))
     S.bvh_builder = abi.RT_BVH_DEVICE_SAH
     cam = S.camera_desc(image_width=48, samples_per_pixel=4, max_depth=6)

@@ -268,6 +268,17 @@ def test_gpu_device_built_trees_find_the_brute_force_hits(builder, arity):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("builder", ["RT_BVH_DEVICE_SAH", "RT_BVH_DEVICE"])
+def test_gpu_device_built_small_tree_finds_the_brute_force_hits(builder):
+    """301 items, most of them visible (in "big" most never cover a pixel
+    centre): a device-built tree that drops or mis-ranges one shows."""
+    b = getattr(abi, builder)
+    out, info = gpu_frame("small-outside", {"bvh_builder": b, "bvh_arity": 2}, None, {"bvh_builder": b, "bvh_arity": 2})
+    assert info["features"] & abi.RT_FEAT_FLAT == 0
+    assert_identical(out, "small-outside", "gfx950 %s" % builder)
+
+
+@pytest.mark.gpu
 def test_gpu_leafshare_variant_finds_the_brute_force_hits():
     """The compacted-leaf-test variant library (tests/test_leaf_share.py), in a
     process of its own: every case through the binary and the 4-wide walk."""
