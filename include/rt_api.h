@@ -53,6 +53,11 @@
  *                     <- no counterpart: DynamicCamera clears its accumulation when the camera
  *                        moves (DynamicCamera.cpp:269-276); these reproject the previous pose's
  *                        displayed image into the new pose and blend it with the new samples
+ *   rt_scene_move_spheres / rt_scene_move_spheres_device / rt_multi_move_spheres
+ *                     <- no counterpart: the reference converts and uploads its scene once
+ *                        (CudaSceneInitialization.cuh:249-300) and DynamicCamera moves only the
+ *                        camera; these move world spheres of a live scene and refit the world
+ *                        BVH's boxes on the device
  *   rt_last_error     <- replaces CUDA_CHECK's exit() and the converters' exceptions
  *                        (CudaMemoryUtility.cuh:9-15, HittableConverter.cuh:103-108): errors are
  *                        returned as negative codes, never thrown or exit()ed across the ABI.
@@ -467,7 +472,10 @@ int rt_render_device(rt_scene *scene, const rt_frame *frame,
    (BVHNode.cpp:215-254, unit traversal and intersection costs).  0 for a flat
    world.  Always the BINARY tree the builder made (for a 4-wide scene, the
    tree before the collapse, costed at creation); otherwise copies the nodes
-   back from the device. */
+   back from the device.  After rt_scene_move_spheres* a binary scene therefore
+   reports the refitted tree -- the caller's signal for when a rebuild (destroy
+   and create) pays -- while a 4-wide scene keeps returning creation's figure:
+   the binary tree it was collapsed from is not kept. */
 int rt_scene_bvh_cost(const rt_scene *scene, double *cost);
 
 /* Run the counter-instrumented kernel variant (untimed) and return totals. */
@@ -904,6 +912,52 @@ int rt_multi_shard_ms(rt_multi *multi, double *ms);
 int rt_multi_gather_ms(rt_multi *multi, double *ms);
 
 int rt_multi_destroy(rt_multi *multi);
+
+/* ---- moving spheres (functions added under ABI 5: no struct or signature
+   above changed) ------------------------------------------------------------
+   A scene is otherwise immutable after rt_scene_create; these move spheres of
+   the world without the host compile, upload and BVH build of a new scene.
+   The world tree keeps its topology and has every box refitted bottom-up on
+   the device from the moved primitives (csrc/rt_refit.hip; DESIGN.md "Moving
+   spheres").  The closest hit does not depend on the tree, so the moved scene
+   renders what a scene freshly created at the new positions renders (same
+   hits; the usual exact-t ties aside); only the tree's quality degrades with
+   the distance moved -- rt_scene_bvh_cost tells.
+
+   object_ids index rt_scene_desc.objects.  A sphere is movable when it is
+   among the world's primitive items -- directly, through lists or under any
+   rotate_y / translate chain -- and does not bound a constant medium.  A
+   move sets the sphere's centre at t = 0 in the item's local frame
+   (rt_object_desc.a); a moving sphere keeps its displacement c1 - c0, so its
+   second centre moves by the same vector; the radius stays.  An entry of the
+   lights list that is the same object follows with it.  Tile dispatch orders
+   measured before the move are kept: they change the order of the work, never
+   a frame.  What the caller accumulated or displayed before the move
+   (progressive sums, adaptive moments, display histories) describes the old
+   scene: the caller resets it. */
+
+/* centres: n x 3 doubles.  Validates everything first, and on any error leaves
+   the scene untouched: an id out of range, an object that is not a sphere
+   among the world's primitive items, an id named twice or a centre that is not
+   finite is RT_ERR_INVALID; a sphere that bounds a constant medium is
+   RT_ERR_UNSUPPORTED (the medium's box and face constants would have to
+   follow).  n = 0 is a no-op.  Synchronous: waits for the scene's pending
+   launches, and the move has completed on return. */
+int rt_scene_move_spheres(rt_scene *scene, int32_t n, const int32_t *object_ids, const double *centres);
+
+/* The same with device arrays, asynchronously on hip_stream (NULL = the HIP
+   null stream): the move joins the scene's launch chain like rt_render_device,
+   so it never overlaps a render of the scene on any stream.  The arrays are
+   read by kernels on hip_stream and may be rewritten by work queued there
+   after the call.  An entry the host variant would refuse is skipped on the
+   device (both entries of an id named twice); the others are applied.  The
+   scene's first move also allocates its refit state (it waits for the scene's
+   own stream then). */
+int rt_scene_move_spheres_device(rt_scene *scene, int32_t n, const int32_t *device_object_ids,
+                                 const double *device_centres, void *hip_stream);
+
+/* rt_scene_move_spheres on every shard's scene.  Host arrays only. */
+int rt_multi_move_spheres(rt_multi *multi, int32_t n, const int32_t *object_ids, const double *centres);
 
 /* ---- guided sampling (one function added under ABI 5: no struct or signature
    above changed) ------------------------------------------------------------

@@ -84,6 +84,19 @@ struct rt_scene {
   hipEvent_t last = nullptr;
   hipStream_t last_st = nullptr;
   bool has_last = false;
+  // Moving spheres (rt_scene_move_spheres*).  Kept from creation: per object of
+  // the description its sphere record when it is a movable world sphere, -1
+  // when it is not among the world's primitive items as a sphere, -2 when it
+  // (also) bounds a medium; the world items' count and the tree's width.  The
+  // first move allocates `refit` -- that table, the per-object counters of a
+  // move, the items' fp64 boxes and rt_refit.hip's links and arrival counters
+  // -- and builds the links; `move_buf` stages the host variant's arrays.
+  std::vector<int32_t> sphere_of;
+  int32_t n_items = 0, bvh_arity = 2;
+  char *refit = nullptr;
+  size_t refit_named = 0, refit_boxes = 0, refit_temp = 0, refit_temp_bytes = 0;
+  char *move_buf = nullptr;
+  size_t move_bytes = 0;
 };
 
 namespace {
@@ -526,6 +539,17 @@ static int apply_residency(rt_scene *s, const rtx::HostScene &H, RtkLdsPlan &pla
   return RT_OK;
 }
 
+// What a move needs of the description after creation (rt_scene::sphere_of).
+static void keep_movable(rt_scene *s, const rt_scene_desc *desc, const rtx::HostScene &H) {
+  s->n_items = (int32_t)H.items.size();
+  s->bvh_arity = H.bvh_arity;
+  s->sphere_of.assign(desc->n_objects, -1);
+  for (const DItem &it : H.items)
+    if (it.kind == I_SPHERE) s->sphere_of[it.id] = it.idx;
+  for (const DItem &it : H.bitems)
+    if (it.kind == I_SPHERE) s->sphere_of[it.id] = -2;
+}
+
 static void fill_info(rt_scene *s, const rtx::HostScene &H, const RtkLdsPlan &plan, int builder) {
   const DScene &d = s->ds;
   rt_scene_info &in = s->info;
@@ -576,6 +600,7 @@ int rt_scene_create_tuned(const rt_scene_desc *desc, int32_t device, const rt_tu
   if (rc == RT_OK) rc = apply_residency(s.get(), H, plan);
   if (rc != RT_OK) return rc;
   fill_info(s.get(), H, plan, builder);
+  keep_movable(s.get(), desc, H);
   *out = s.release();
   return RT_OK;
 }
@@ -600,6 +625,8 @@ int rt_scene_destroy(rt_scene *s) {
   bury(s, s->scratch);
   bury(s, s->probe_buf);
   bury(s, s->list_order);
+  bury(s, s->refit);
+  bury(s, s->move_buf);
   for (auto &o : s->order) bury(s, o.tile_cost); // the slot's one allocation
   bury(s, s->block);
   if (s->last) (void)hipEventDestroy(s->last);
@@ -1284,10 +1311,130 @@ int rt_scene_bvh_cost(const rt_scene *s, double *cost) {
   if (s->ds.root_is_leaf || n <= 0) return RT_OK;
   std::vector<DNode> nodes(n);
   DeviceGuard g(s->device);
+  if (s->has_last) (void)hipEventSynchronize(s->last); // a move's refit on a caller stream
   hipError_t e = hipMemcpy(nodes.data(), s->ds.nodes, sizeof(DNode) * n, hipMemcpyDeviceToHost);
   if (e != hipSuccess) return hip_err(e, "hipMemcpy nodes");
   *cost = rtx::bvh_sah_cost(nodes);
   return RT_OK;
+}
+
+// ---------------------------------------------------------------- moving spheres
+// The state of the scene's first move: one allocation, the movable-sphere
+// table uploaded and the tree's links built on `st` (the move's stream; later
+// moves on other streams follow through the launch chain).
+static int ensure_refit(rt_scene *s, hipStream_t st) {
+  if (s->refit) return RT_OK;
+  const DScene &d = s->ds;
+  const bool tree = !d.root_is_leaf && d.n_nodes > 0;
+  const size_t n_obj = s->sphere_of.size();
+  size_t bytes = 0;
+  auto add = [&](size_t b) {
+    const size_t off = bytes;
+    bytes += align256(b ? b : 1);
+    return off;
+  };
+  add(sizeof(int32_t) * n_obj); // sphere_of, at 0
+  s->refit_named = add(sizeof(unsigned) * n_obj);
+  s->refit_boxes = add(tree ? 6 * sizeof(double) * (size_t)s->n_items : 0);
+  s->refit_temp_bytes = tree ? rtk_refit_temp_bytes(s->n_items, d.n_nodes) : 0;
+  s->refit_temp = add(s->refit_temp_bytes);
+  char *buf = nullptr;
+  hipError_t e = scene_alloc(s, (void **)&buf, bytes);
+  if (e != hipSuccess) return set_err(RT_ERR_OOM, std::string("hipMallocFromPoolAsync refit: ") + hipGetErrorString(e));
+  e = hipMemcpyAsync(buf, s->sphere_of.data(), sizeof(int32_t) * n_obj, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && tree)
+    e = rtk_refit_links(d.nodes, s->bvh_arity, d.n_nodes, buf + s->refit_temp, s->refit_temp_bytes, st);
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(st); // nothing may still use buf
+    scene_free(s, buf);
+    return hip_err(e, "refit links");
+  }
+  s->refit = buf;
+  return RT_OK;
+}
+
+// One move on `st`, a link of the scene's launch chain: the centres, then
+// every world item's box from the tables and a full refit of the tree.
+static int move_on_stream(rt_scene *s, int32_t n, const int32_t *d_ids, const double *d_centres, hipStream_t st) {
+  int rc = order_after_last(s, st);
+  if (rc) return rc;
+  if ((rc = ensure_refit(s, st))) return rc;
+  const DScene &d = s->ds;
+  RefitMove m{};
+  m.ids = d_ids;
+  m.centres = d_centres;
+  m.n = n;
+  m.n_objects = (int32_t)s->sphere_of.size();
+  m.sphere_of = (const int32_t *)s->refit;
+  m.named = (unsigned *)(s->refit + s->refit_named);
+  m.spheres = const_cast<DSphere *>(d.spheres);
+  m.roots = const_cast<DRoot *>(d.roots);
+  m.root_items = d.items;
+  m.n_roots = d.n_roots;
+  hipError_t e = rtk_move_spheres(&m, st);
+  if (e == hipSuccess && !d.root_is_leaf && d.n_nodes > 0) {
+    double *boxes = (double *)(s->refit + s->refit_boxes);
+    e = rtk_item_boxes(d.items, s->n_items, d.spheres, d.quads, d.xforms, boxes, st);
+    if (e == hipSuccess)
+      e = rtk_refit_boxes(const_cast<DNode *>(d.nodes), s->bvh_arity, d.n_nodes, s->n_items, boxes,
+                          s->refit + s->refit_temp, s->refit_temp_bytes, st);
+  }
+  // whatever was queued reads and writes the scene's tables: the chain ends after it either way
+  rc = mark_last(s, st);
+  if (e != hipSuccess) return hip_err(e, "move spheres");
+  return rc;
+}
+
+// what the host variant refuses (the device variant skips the same entries)
+static int check_move(const rt_scene *s, int32_t n, const int32_t *ids, const double *centres) {
+  std::vector<char> seen(s->sphere_of.size(), 0);
+  for (int32_t j = 0; j < n; ++j) {
+    const int32_t id = ids[j];
+    const std::string at = "entry " + std::to_string(j) + ": object " + std::to_string(id);
+    if (id < 0 || (size_t)id >= s->sphere_of.size()) return set_err(RT_ERR_INVALID, at + " is out of range");
+    if (s->sphere_of[id] == -2)
+      return set_err(RT_ERR_UNSUPPORTED, at + " bounds a constant medium: its boundary constants would have to follow");
+    if (s->sphere_of[id] < 0)
+      return set_err(RT_ERR_INVALID, at + " is not a sphere among the world's primitive items");
+    if (seen[id]) return set_err(RT_ERR_INVALID, at + " is named twice");
+    seen[id] = 1;
+    for (int a = 0; a < 3; ++a)
+      if (!std::isfinite(centres[3 * (size_t)j + a])) return set_err(RT_ERR_INVALID, at + ": the centre is not finite");
+  }
+  return RT_OK;
+}
+
+int rt_scene_move_spheres(rt_scene *s, int32_t n, const int32_t *object_ids, const double *centres) {
+  if (!s || n < 0) return set_err(RT_ERR_INVALID, "null scene or negative count");
+  if (n == 0) return RT_OK;
+  if (!object_ids || !centres) return set_err(RT_ERR_INVALID, "null argument");
+  int rc = check_move(s, n, object_ids, centres);
+  if (rc) return rc;
+  DeviceGuard g(s->device);
+  const size_t id_bytes = align256(sizeof(int32_t) * (size_t)n), c_bytes = 3 * sizeof(double) * (size_t)n;
+  // only this function uses move_buf, on the scene's stream, and synchronises before it returns
+  if ((rc = grow(s, s->move_buf, s->move_bytes, id_bytes + c_bytes, Idle::Already, "hipMallocFromPoolAsync move")))
+    return rc;
+  hipError_t e = hipMemcpyAsync(s->move_buf, object_ids, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, s->stream);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(s->move_buf + id_bytes, centres, c_bytes, hipMemcpyHostToDevice, s->stream);
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(s->stream);
+    return hip_err(e, "move upload");
+  }
+  rc = move_on_stream(s, n, (const int32_t *)s->move_buf, (const double *)(s->move_buf + id_bytes), s->stream);
+  e = hipStreamSynchronize(s->stream);
+  if (rc) return rc;
+  return e == hipSuccess ? RT_OK : hip_err(e, "move spheres");
+}
+
+int rt_scene_move_spheres_device(rt_scene *s, int32_t n, const int32_t *device_object_ids,
+                                 const double *device_centres, void *hip_stream) {
+  if (!s || n < 0) return set_err(RT_ERR_INVALID, "null scene or negative count");
+  if (n == 0) return RT_OK;
+  if (!device_object_ids || !device_centres) return set_err(RT_ERR_INVALID, "null argument");
+  DeviceGuard g(s->device);
+  return move_on_stream(s, n, device_object_ids, device_centres, (hipStream_t)hip_stream);
 }
 
 int rt_last_kernel_ms(rt_scene *s, double *ms) {
@@ -1553,6 +1700,14 @@ int rt_multi_render(rt_multi *m, const rt_frame *f, const rt_render_params *p, d
   e = hipMemcpyAsync(host_rgb, m->frame, frame_d * sizeof(double), hipMemcpyDeviceToHost, root->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(root->stream);
   if (e != hipSuccess) return hip_err(e, "frame D2H");
+  return RT_OK;
+}
+
+int rt_multi_move_spheres(rt_multi *m, int32_t n, const int32_t *object_ids, const double *centres) {
+  if (!m) return set_err(RT_ERR_INVALID, "null argument");
+  // the shards hold one description: what the first refuses none has applied
+  for (rt_scene *s : m->scenes)
+    if (int rc = rt_scene_move_spheres(s, n, object_ids, centres)) return rc;
   return RT_OK;
 }
 

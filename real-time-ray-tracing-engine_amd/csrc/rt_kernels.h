@@ -1,6 +1,6 @@
 // rt_kernels.h — every rtk_* launcher, declared once: included by the files
 // that define them (rt_kernel.hip, rt_frame.hip, rt_adaptive.hip, rt_guides.hip,
-// rt_denoise.hip, rt_temporal.hip, rt_bvh_build.hip, rt_bvh_sah.hip) and by their caller (rt_api.cpp), so a
+// rt_denoise.hip, rt_temporal.hip, rt_bvh_build.hip, rt_bvh_sah.hip, rt_refit.hip) and by their caller (rt_api.cpp), so a
 // definition whose parameter list drifts from its callers' no longer compiles.
 #ifndef RT_KERNELS_H
 #define RT_KERNELS_H
@@ -112,6 +112,36 @@ size_t rtk_sah_temp_bytes(int n);
 hipError_t rtk_build_sah(const double *boxes, const DItem *items_in, int n, DNode *nodes, DItem *items_out,
                          void *temp, size_t temp_bytes, int stack_budget, int *n_nodes, int *depth,
                          int *root_leaf, hipStream_t st);
+
+// ---- rt_refit.hip: moved spheres and the bottom-up refit of the world tree's boxes.
+// nodes: DNode (arity 2) or DNode4 (arity 4) records.  temp (rtk_refit_temp_bytes) holds the
+// links rtk_refit_links builds once per tree and the arrival counters each rtk_refit_boxes clears;
+// boxes: n_items x (lo xyz, hi xyz) fp64 in leaf order.  rtk_refit = links + one refit (tests).
+size_t rtk_refit_temp_bytes(int n_items, int n_nodes);
+hipError_t rtk_refit_links(const void *nodes, int arity, int n_nodes, void *temp, size_t temp_bytes, hipStream_t st);
+hipError_t rtk_refit_boxes(void *nodes, int arity, int n_nodes, int n_items, const double *boxes, void *temp,
+                           size_t temp_bytes, hipStream_t st);
+hipError_t rtk_refit(void *nodes, int arity, int n_nodes, int root_leaf, const DItem *items, int n_items,
+                     const double *boxes, void *temp, size_t temp_bytes, hipStream_t st);
+// each world item's fp64 box from the tables (rt_refit.h item_box)
+hipError_t rtk_item_boxes(const DItem *items, int n_items, const DSphere *spheres, const DQuad *quads,
+                          const DXform *xforms, double *boxes, hipStream_t st);
+// One move: entry j sets spheres[sphere_of[ids[j]]].c0 = centres[j] (and the matching roots[] copy
+// of a flat world, root_items its items) when ids[j] is in [0, n_objects), sphere_of[] of it is
+// >= 0, no other applicable entry names it and the centre is finite; any other entry is skipped.
+// named: n_objects counters (scratch).
+struct RefitMove {
+  const int32_t *ids;
+  const double *centres;
+  int32_t n, n_objects;
+  const int32_t *sphere_of;
+  unsigned *named;
+  DSphere *spheres;
+  DRoot *roots;
+  const DItem *root_items;
+  int32_t n_roots, pad_;
+};
+hipError_t rtk_move_spheres(const RefitMove *m, hipStream_t st);
 
 } // extern "C"
 #endif

@@ -257,4 +257,5 @@ EXPORTS = (
     "rt_denoise_variance_workspace_bytes", "rt_denoise_variance_device",
     "rt_history_variance_bytes", "rt_temporal_variance_device", "rt_denoise_given_variance_device",
     "rt_guided_select_device",
+    "rt_scene_move_spheres", "rt_scene_move_spheres_device", "rt_multi_move_spheres",
 )

@@ -245,7 +245,9 @@ class AdaptiveRenderer:
         return self.ops.bytes(self.acc, self.tile_strata, self.frame)
 
     def reset(self, frame=None):
-        """Camera moved: clear every buffer, all tiles active again."""
+        """Camera moved: clear every buffer, all tiles active again.
+        Also after Renderer.move_spheres: what was accumulated (the sums and the moments) describes the old
+        scene, and nothing here notices the move -- the caller calls reset()."""
         if frame is not None:
             self.frame = frame
         if (self.frame.image_width, self.frame.image_height) != self._shape:

@@ -523,7 +523,10 @@ class DenoisedDisplay:
         return self.bytes(out)
 
     def reset(self, frame=None):
-        """Camera moved: the wrapped renderer restarts, the guides are cleared."""
+        """Camera moved: the wrapped renderer restarts, the guides are cleared.
+        Also after Renderer.move_spheres: the accumulator and the guide sums
+        describe the old scene, and nothing here notices the move -- the caller
+        calls reset()."""
         self.pr.reset(frame)
         if (self.pr.frame.image_width, self.pr.frame.image_height) != self._shape:
             self._allocate()

@@ -59,7 +59,9 @@ class ProgressiveRenderer:
         return self.acc * self.scale
 
     def reset(self, frame=None):
-        """Camera moved (DynamicCamera.cpp:269-276): clear and restart."""
+        """Camera moved (DynamicCamera.cpp:269-276): clear and restart.
+        Also after Renderer.move_spheres: what was accumulated describes the old
+        scene, and nothing here notices the move -- the caller calls reset()."""
         if frame is not None:
             self.frame = frame
         self.acc.zero_()

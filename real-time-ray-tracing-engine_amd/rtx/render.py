@@ -15,6 +15,25 @@ from .lib import check, load
 from .ppm import write_ppm
 
 
+def _move_arrays(ids, centres):
+    ids = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+    centres = np.ascontiguousarray(centres, dtype=np.float64).reshape(-1, 3)
+    if len(ids) != len(centres):
+        raise ValueError("%d ids, %d centres" % (len(ids), len(centres)))
+    return ids, centres
+
+
+def describe_move(scene, ids, centres):
+    """The move in the SceneDescription: the centre, and for a sphere given by
+    its two centres the second one shifted by the same vector (the device keeps
+    the displacement c1 - c0; the stored form holds that displacement itself)."""
+    for i, c in zip(ids, centres):
+        o = scene.objects[int(i)]
+        if o.moving == 1:
+            o.b = abi.Vec3.of([o.b.x + (c[0] - o.a.x), o.b.y + (c[1] - o.a.y), o.b.z + (c[2] - o.a.z)])
+        o.a = abi.Vec3.of([float(c[0]), float(c[1]), float(c[2])])
+
+
 def camera_frame(cam):
     """Camera::initialize (Camera.cpp:31-73) via rt_camera_setup."""
     f = abi.Frame()
@@ -158,6 +177,27 @@ class Renderer:
         check(self.lib.rt_last_kernel_ms(self.handle, C.byref(ms)))
         return ms.value
 
+    def move_spheres(self, ids, centres):
+        """rt_scene_move_spheres: the world spheres `ids` (object indices of the
+        description) get the centres `centres` ([n, 3]); the world BVH is
+        refitted on the device.  Synchronous.  The SceneDescription the
+        renderer was made from is updated too, so a later Renderer(scene) or
+        dump_scene(scene) describes the moved scene.  Whatever was accumulated
+        or displayed before the move (progressive.py, adaptive.py, the display
+        classes) describes the old scene: reset() it."""
+        ids, centres = _move_arrays(ids, centres)
+        check(self.lib.rt_scene_move_spheres(self.handle, len(ids), ids.ctypes.data_as(C.POINTER(C.c_int32)),
+                                             centres.ctypes.data_as(C.POINTER(C.c_double))))
+        describe_move(self.scene_desc, ids, centres)
+
+    def move_spheres_device(self, ids_ptr, centres_ptr, n, stream_ptr=None):
+        """rt_scene_move_spheres_device: the same from device arrays (int32 [n],
+        float64 [n, 3]) asynchronously on `stream_ptr`; an entry move_spheres
+        would refuse is skipped.  The SceneDescription is not touched: the
+        host does not see the arrays."""
+        check(self.lib.rt_scene_move_spheres_device(self.handle, int(n), C.c_void_p(ids_ptr),
+                                                    C.c_void_p(centres_ptr), C.c_void_p(stream_ptr or 0)))
+
 
 class MultiRenderer:
     """rt_multi_*: one device scene per shard (shard k on devices[k % len]),
@@ -166,6 +206,7 @@ class MultiRenderer:
 
     def __init__(self, scene, devices=(0,), shards=None, tuning=None):
         self.lib = load()
+        self.scene_desc = scene
         self._desc = scene.desc()
         self._tuning = abi.tuning(tuning)
         devs = (C.c_int32 * len(devices))(*devices)
@@ -197,6 +238,13 @@ class MultiRenderer:
         check(self.lib.rt_multi_render(self.handle, C.byref(frame), C.byref(p),
                                        out.ctypes.data_as(C.POINTER(C.c_double))))
         return out
+
+    def move_spheres(self, ids, centres):
+        """rt_multi_move_spheres: Renderer.move_spheres on every shard's scene."""
+        ids, centres = _move_arrays(ids, centres)
+        check(self.lib.rt_multi_move_spheres(self.handle, len(ids), ids.ctypes.data_as(C.POINTER(C.c_int32)),
+                                             centres.ctypes.data_as(C.POINTER(C.c_double))))
+        describe_move(self.scene_desc, ids, centres)
 
     def shard_ms(self):
         ms = (C.c_double * self.n_shards)()

@@ -489,7 +489,11 @@ class TemporalDisplay:
             self._allocate()
 
     def clear(self):
-        """Forget the history (the scene changed): the next frames start from the samples alone."""
+        """Forget the history (the scene changed): the next frames start from the samples alone.
+        After Renderer.move_spheres the caller calls reset() and then clear():
+        the reprojection follows the camera only, it has no motion vectors, so
+        a history of the old scene would be blended onto moved objects (object
+        motion in the temporal displays is future work)."""
         self.frame_prev = self._shown = None
 
 

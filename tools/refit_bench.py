@@ -1,0 +1,171 @@
+#!/usr/bin/env python3
+"""Moving spheres measured.
+
+    python tools/refit_bench.py [--sizes 486 100000 1000000] [--reps 20] [--log profiles/refit_bench.log]
+
+Per size -- 486: bouncing_seed42 (bench.py's C3 scene, host tree, binary);
+otherwise that many random spheres in [-50, 50]^3 over a ground sphere
+(tests/test_device_bvh.py's world; from 65536 the device SAH builder, from 4096
+a 4-wide tree) -- one JSON line each for
+
+  move      move_ms: one rt_scene_move_spheres_device of every sphere but the
+            ground (centres, item boxes, full refit), the mean of `reps` calls
+            between HIP events; recreate_ms: rt_scene_destroy + rt_scene_create
+            of the same description, host clock, the best of 3 (the host
+            compile, the upload and the BVH build a move replaces);
+  walk      after 1, 10 and 100 steps of a random walk (every step adds a vector
+            uniform in [-step, step]^3 to every moved sphere; step is stated in
+            the line): frame_ms of one-stratum 1080p frames (HIP events, the
+            mean of `reps`) and rt_scene_bvh_cost of the refitted scene, beside
+            the same of a scene freshly created at those positions, and the
+            largest pixel difference between the two scenes' frames.
+            rt_scene_bvh_cost of a 4-wide scene is creation's figure (rt_api.h):
+            there only frame_ms shows the refitted tree's quality.
+
+The lines go to stdout and to --log.  No test asserts any of these numbers."""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "real-time-ray-tracing-engine_amd")
+sys.path.insert(0, PKG)
+
+import numpy as np  # noqa: E402
+
+LOG = None
+
+
+def say(**kw):
+    line = json.dumps(kw)
+    print(line, flush=True)
+    if LOG:
+        LOG.write(line + "\n")
+        LOG.flush()
+
+
+def random_world(n, seed=1):
+    """tests/test_device_bvh.py random_spheres, built without the JSON detour."""
+    from rtx import abi
+    from rtx.scene import SceneDescription
+    rng = np.random.default_rng(seed)
+    c, r = rng.uniform(-50, 50, size=(n, 3)), rng.uniform(0.05, 0.4, size=n)
+    S = SceneDescription()
+    S.camera = {"aspect_ratio": 1.0, "vfov": 50.0, "lookfrom": [0, 20, 110], "lookat": [0, 0, 0],
+                "background": [0.7, 0.8, 1.0]}
+    mats = [S.add_material(abi.RT_MAT_LAMBERTIAN, texture=S.add_texture(abi.RT_TEX_SOLID, color=(0.5, 0.5, 0.5))),
+            S.add_material(abi.RT_MAT_METAL, albedo=(0.8, 0.7, 0.6), fuzz=0.1),
+            S.add_material(abi.RT_MAT_DIELECTRIC, refraction_index=1.5)]
+    ids = [S.add_object(abi.RT_OBJ_SPHERE, material=mats[k % 3], a=c[k], s=r[k]) for k in range(n)]
+    ids.append(S.add_object(abi.RT_OBJ_SPHERE, material=mats[0], a=(0, -1000, 0), s=940))
+    S.world = S.add_list(ids)
+    return S
+
+
+def world(n):
+    from rtx.scene import load_scene
+    if n == 486:
+        return load_scene(os.path.join(PKG, "scenes", "bouncing_seed42.json")), 0.05
+    return random_world(n), 0.5
+
+
+def frame_ms(torch, R, frame, buf, reps):
+    """Mean device ms of a one-stratum frame (a progressive step), and the frame of stratum 0."""
+    from rtx import abi
+    stream = torch.cuda.current_stream()
+    strata = frame.sqrt_spp * frame.sqrt_spp
+
+    def step(k, acc):
+        R.render_device(frame, buf.data_ptr(), stream.cuda_stream, seed=5, samples=(k % strata, 1),
+                        output=abi.RT_OUT_SUM, accumulate=acc)
+    for k in range(3):
+        step(k, 1)
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    t0.record(stream)
+    for k in range(reps):
+        step(k, 1)
+    t1.record(stream)
+    t1.synchronize()
+    step(0, 0)
+    torch.cuda.synchronize()
+    return t0.elapsed_time(t1) / reps, buf.cpu().numpy().copy()
+
+
+def main():
+    global LOG
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--sizes", type=int, nargs="+", default=[486, 100000, 1000000])
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--log", default=os.path.join(ROOT, "profiles", "refit_bench.log"))
+    args = ap.parse_args()
+    import torch
+    from rtx import abi
+    from rtx.lib import check
+    from rtx.render import Renderer, camera_frame, describe_move
+    os.makedirs(os.path.dirname(os.path.abspath(args.log)), exist_ok=True)
+    LOG = open(args.log, "a")
+    for n in args.sizes:
+        S, step = world(n)
+        cam = S.camera_desc(image_width=1920, aspect_ratio=16.0 / 9.0, samples_per_pixel=64, max_depth=8)
+        frame = camera_frame(cam)
+        spheres = [i for i, o in enumerate(S.objects) if o.kind == abi.RT_OBJ_SPHERE and o.s < 100]
+        ids = np.array(spheres, dtype=np.int32)
+        home = np.array([[S.objects[i].a.x, S.objects[i].a.y, S.objects[i].a.z] for i in spheres])
+        d_ids = torch.from_numpy(ids).cuda()
+        buf = torch.zeros((frame.image_height, frame.image_width, 3), dtype=torch.float64, device="cuda")
+        stream = torch.cuda.current_stream()
+        t = time.perf_counter()
+        R = Renderer(S)
+        create_ms = [(time.perf_counter() - t) * 1e3]
+        info = R.info()
+        tree = dict(spheres=len(spheres), builder=info["bvh_builder"], arity=info["bvh_arity"], nodes=info["n_nodes"])
+        for _ in range(3):  # destroy + create through the ABI alone: the description's ctypes view is kept
+            h = C.c_void_p()
+            t = time.perf_counter()
+            check(R.lib.rt_scene_destroy(R.handle))
+            check(R.lib.rt_scene_create(C.byref(R._desc), 0, C.byref(h)))
+            create_ms.append((time.perf_counter() - t) * 1e3)
+            R.handle = h
+        # one move of everything: to where it is (the refit does the same work wherever the centres go)
+        d_home = torch.from_numpy(home).cuda()
+        move = lambda d_c: R.move_spheres_device(d_ids.data_ptr(), d_c.data_ptr(), len(ids), stream.cuda_stream)  # noqa: E731
+        for _ in range(3):
+            move(d_home)
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        t0.record(stream)
+        for _ in range(args.reps):
+            move(d_home)
+        t1.record(stream)
+        t1.synchronize()
+        say(kind="move", n=n, **tree, move_ms=t0.elapsed_time(t1) / args.reps, recreate_ms=min(create_ms[1:]),
+            first_create_with_python_ms=create_ms[0])
+        ms0, _ = frame_ms(torch, R, frame, buf, args.reps)
+        say(kind="walk", n=n, steps=0, step=step, frame_ms=ms0, bvh_cost=R.bvh_cost())
+        rng = np.random.default_rng(9)
+        at, done = home.copy(), 0
+        for upto in (1, 10, 100):
+            while done < upto:
+                at = at + rng.uniform(-step, step, size=at.shape)
+                d_at = torch.from_numpy(at).cuda()
+                move(d_at)
+                done += 1
+            torch.cuda.synchronize()
+            ms, img = frame_ms(torch, R, frame, buf, args.reps)
+            cost = R.bvh_cost()
+            describe_move(S, ids, at)
+            with Renderer(S) as F:
+                fms, fimg = frame_ms(torch, F, frame, buf, args.reps)
+                fcost = F.bvh_cost()
+            say(kind="walk", n=n, steps=upto, step=step, frame_ms=ms, fresh_frame_ms=fms, slowdown=ms / fms,
+                bvh_cost=cost, fresh_bvh_cost=fcost, max_pixel_diff=float(np.nanmax(np.abs(img - fimg))))
+        R.close()
+    LOG.close()
+
+
+if __name__ == "__main__":
+    main()
