@@ -473,9 +473,10 @@ int rt_render_device(rt_scene *scene, const rt_frame *frame,
    world.  Always the BINARY tree the builder made (for a 4-wide scene, the
    tree before the collapse, costed at creation); otherwise copies the nodes
    back from the device.  After rt_scene_move_spheres* a binary scene therefore
-   reports the refitted tree -- the caller's signal for when a rebuild (destroy
-   and create) pays -- while a 4-wide scene keeps returning creation's figure:
-   the binary tree it was collapsed from is not kept. */
+   reports the refitted tree -- the caller's signal for when a rebuild
+   (rt_scene_rebuild_bvh) pays -- while a 4-wide scene keeps returning the
+   figure of the binary tree it was last collapsed from, which is not kept:
+   creation's, and after rt_scene_rebuild_bvh the rebuilt binary tree's. */
 int rt_scene_bvh_cost(const rt_scene *scene, double *cost);
 
 /* Run the counter-instrumented kernel variant (untimed) and return totals. */
@@ -958,6 +959,37 @@ int rt_scene_move_spheres_device(rt_scene *scene, int32_t n, const int32_t *devi
 
 /* rt_scene_move_spheres on every shard's scene.  Host arrays only. */
 int rt_multi_move_spheres(rt_multi *multi, int32_t n, const int32_t *object_ids, const double *centres);
+
+/* ---- rebuilding the world BVH (functions added under ABI 5: no struct or
+   signature above changed) ---------------------------------------------------
+   A refit keeps the topology chosen at creation, and the tree degrades as the
+   spheres drift.  rt_scene_rebuild_bvh builds a new tree over the world items
+   where they are now, entirely on the device (csrc/rt_bvh_sah.hip, and
+   csrc/rt_collapse.hip for a 4-wide scene; DESIGN.md "Rebuild"), without the
+   host compile and the uploads of a new scene: the tree, the scene info, the
+   SAH cost and therefore every frame are those of a scene freshly created from
+   the moved description with bvh_builder = RT_BVH_DEVICE_SAH and the same
+   arity and tuning, bit for bit.  Tile dispatch orders are kept.
+
+   Synchronous, like rt_scene_move_spheres: waits for the scene's pending
+   launches, and the new tree is live on return.  *rebuilt (may be NULL) is 1
+   when the new tree was taken.  It is 0, with RT_OK and the scene exactly as it
+   was (its refitted tree), when the world is flat, when the builder makes the
+   world one leaf (the scene's kernel instance is fixed at creation), when the
+   new tree is deeper than the traversal stack or rt_tuning.lbvh_max_depth
+   allows, or when a 4-wide scene's collapse or the LDS plan does not fit at
+   the new depth.  The arity never changes; rt_scene_info.bvh_builder becomes
+   RT_BVH_DEVICE_SAH.  The first rebuild allocates the scene's rebuild state
+   (staging for the tree and the items, the builder's workspace), kept until
+   rt_scene_destroy; a scene created by the host builder also gets a node range
+   large enough for any tree over its items, counted in
+   rt_scene_info.device_bytes.  RT_ERR_INVALID: a null scene.  A device failure
+   is RT_ERR_DEVICE. */
+int rt_scene_rebuild_bvh(rt_scene *scene, int32_t *rebuilt);
+
+/* rt_scene_rebuild_bvh on every shard's scene; *rebuilt is 1 only if every
+   shard took its new tree. */
+int rt_multi_rebuild_bvh(rt_multi *multi, int32_t *rebuilt);
 
 /* ---- guided sampling (one function added under ABI 5: no struct or signature
    above changed) ------------------------------------------------------------

@@ -97,6 +97,24 @@ struct rt_scene {
   size_t refit_named = 0, refit_boxes = 0, refit_temp = 0, refit_temp_bytes = 0;
   char *move_buf = nullptr;
   size_t move_bytes = 0;
+  // Rebuilding the world tree (rt_scene_rebuild_bvh).  Kept from creation: the
+  // world items in compile order -- what a device build starts from, whatever
+  // order the live table's leaves have put them in -- the counts the
+  // residency plan reads, the binary tree's depth and the 4-wide tree's levels,
+  // and the room of the block's node range.  The first rebuild allocates
+  // `rebuild` (the Rebuild offsets: those items, their boxes, the staged binary
+  // tree, 4-wide tree and leaf-ordered items, the builder's and the collapse's
+  // temp) and keeps it; `own_nodes` is the node range of a host-built scene,
+  // whose block holds its creation tree and no more.
+  std::vector<DItem> compile_items;
+  int32_t n_spheres = 0, n_perlin = 0;
+  int32_t bvh_depth = 0, bvh_depth4 = 0;
+  size_t node_room = 0; // bytes of the node range d.nodes points into
+  struct Rebuild { // offsets into `rebuild`; the builder and the collapse run in turn and share temp
+    size_t items = 0, boxes = 0, nodes = 0, nodes4 = 0, sorted = 0, temp = 0, temp_bytes = 0;
+  } rb;
+  char *rebuild = nullptr;
+  char *own_nodes = nullptr;
 };
 
 namespace {
@@ -424,6 +442,8 @@ static int open_scene(int32_t device, const rt_tuning &tune, const rtx::HostScen
     using T = typename std::decay_t<decltype(v)>::value_type;
     char *dst = s->block + L.table_off[i++];
     s->ds.*dm = (const T *)dst;
+    if (std::is_same<T, DNode>::value) // the range's room, to the next table (rt_scene_rebuild_bvh)
+      s->node_room = (i < L.table_off.size() ? L.table_off[i] : L.stats_off) - L.table_off[i - 1];
     const bool on_device = std::is_same<T, DNode>::value && H.device_bvh; // built there, below
     if (e == hipSuccess && !v.empty() && !on_device)
       e = upload(s.get(), dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
@@ -499,11 +519,22 @@ static int collapse_world_tree(rt_scene *s, rtx::HostScene &H, bool want4) {
 // The traversal stack and what the scene's blocks keep in LDS: the attributes
 // of the instances the scene runs and the device's CU count into the residency
 // plan (rt_lds_plan.h), its outcome into the DScene and the wave-slot counts.
-static int apply_residency(rt_scene *s, const rtx::HostScene &H, RtkLdsPlan &plan) {
-  DScene &d = s->ds;
+// In two steps: plan_residency computes it for a tree of `n_nodes` nodes and
+// the depths s->bvh_depth / bvh_depth4 (creation's tree, or the one a rebuild
+// has staged) and touches nothing; commit_residency makes it the scene's.
+struct Residency {
+  int32_t stack_depth = 0;
+  SceneLdsPlan p{};
+};
+static int plan_residency(const rt_scene *s, int32_t n_nodes, int32_t bvh_depth, int32_t bvh_depth4, Residency &r) {
+  const DScene &d = s->ds;
   std::string err;
-  d.stack_depth = rtx::traversal_stack_depth(H, err);
-  if (!d.stack_depth) return set_err(RT_ERR_UNSUPPORTED, err);
+  rtx::HostScene shape; // traversal_stack_depth reads the tree's shape only
+  shape.bvh_depth = bvh_depth;
+  shape.bvh_arity = s->bvh_arity;
+  shape.bvh_depth4 = bvh_depth4;
+  r.stack_depth = rtx::traversal_stack_depth(shape, err);
+  if (!r.stack_depth) return set_err(RT_ERR_UNSUPPORTED, err);
   LdsPlanInput in{};
   hipError_t e = rtk_instance_attrs(d.features, 0, &in.render);
   if (e == hipSuccess) e = hipDeviceGetAttribute(&in.cus, hipDeviceAttributeMultiprocessorCount, s->device);
@@ -514,15 +545,21 @@ static int apply_residency(rt_scene *s, const rtx::HostScene &H, RtkLdsPlan &pla
   // (a failed CU-count query is reported under the same name, as it always was)
   if (e != hipSuccess) return set_err(RT_ERR_DEVICE, std::string("hipFuncGetAttributes: ") + hipGetErrorString(e));
   in.features = d.features;
-  in.stack_depth = d.stack_depth;
-  in.n_nodes = d.n_nodes;
-  in.n_items = (int32_t)H.items.size();
-  in.n_spheres = (int32_t)H.spheres.size();
-  in.n_perlin = (int32_t)H.perlin.size();
-  const SceneLdsPlan p = plan_scene_lds(in, s->tune);
-  plan = p.render;
-  if (p.outcome == LDS_UNSUPPORTED)
+  in.stack_depth = r.stack_depth;
+  in.n_nodes = n_nodes;
+  in.n_items = s->n_items;
+  in.n_spheres = s->n_spheres;
+  in.n_perlin = s->n_perlin;
+  r.p = plan_scene_lds(in, s->tune);
+  if (r.p.outcome == LDS_UNSUPPORTED)
     return set_err(RT_ERR_UNSUPPORTED, "BVH traversal stacks exceed the per-block LDS limit");
+  return RT_OK;
+}
+static void commit_residency(rt_scene *s, const Residency &r, RtkLdsPlan &plan) {
+  DScene &d = s->ds;
+  const SceneLdsPlan &p = r.p;
+  plan = p.render;
+  d.stack_depth = r.stack_depth;
   if (p.outcome == LDS_STACKS_OVER_SHARE)
     std::fprintf(stderr,
                  "rtx: traversal stacks need %d B of LDS per block, above the %d B share at %d "
@@ -536,39 +573,38 @@ static int apply_residency(rt_scene *s, const rtx::HostScene &H, RtkLdsPlan &pla
   d.lds_items_pc = p.lds_items_pc;
   d.lds_spheres_pc = p.lds_spheres_pc;
   d.lds_perlin = p.lds_perlin;
-  return RT_OK;
 }
 
-// What a move needs of the description after creation (rt_scene::sphere_of).
-static void keep_movable(rt_scene *s, const rt_scene_desc *desc, const rtx::HostScene &H) {
+// What a move and a rebuild need of the description after creation
+// (rt_scene::sphere_of, compile_items and the counts beside them).  Takes the
+// compile-order items out of H: the last reader of H.items is gone by then.
+static void keep_movable(rt_scene *s, const rt_scene_desc *desc, rtx::HostScene &H) {
   s->n_items = (int32_t)H.items.size();
+  s->n_spheres = (int32_t)H.spheres.size();
+  s->n_perlin = (int32_t)H.perlin.size();
   s->bvh_arity = H.bvh_arity;
+  s->bvh_depth = H.bvh_depth;
+  s->bvh_depth4 = H.bvh_depth4;
   s->sphere_of.assign(desc->n_objects, -1);
   for (const DItem &it : H.items)
     if (it.kind == I_SPHERE) s->sphere_of[it.id] = it.idx;
   for (const DItem &it : H.bitems)
     if (it.kind == I_SPHERE) s->sphere_of[it.id] = -2;
+  // a host build left H.items in leaf order and handed the compile order over;
+  // a device build sorted the device's copy only
+  s->compile_items = std::move(H.compile_items.empty() ? H.items : H.compile_items);
 }
 
-static void fill_info(rt_scene *s, const rtx::HostScene &H, const RtkLdsPlan &plan, int builder) {
+// The part of rt_scene_info a rebuild changes: the tree's size and depth, who
+// built it, and the residency plan that follows from them.
+static void fill_tree_info(rt_scene *s, const RtkLdsPlan &plan, int builder) {
   const DScene &d = s->ds;
   rt_scene_info &in = s->info;
-  std::memset(&in, 0, sizeof in);
   in.n_nodes = d.n_nodes;
-  in.n_leaf_refs = (int32_t)H.items.size(); // leaves are item ranges
-  in.n_spheres = (int32_t)H.spheres.size();
-  in.n_quads = (int32_t)H.quads.size();
-  in.n_objects = (int32_t)(H.items.size() + H.mitems.size());
-  in.n_light_leaves = (int32_t)H.lights.size();
-  in.bvh_depth = H.bvh_depth;
-  in.node_bytes = (int32_t)(H.bvh_arity == 4 ? sizeof(DNode4) : sizeof(DNode));
-  in.sphere_bytes = (int32_t)sizeof(DSphere);
-  in.quad_bytes = (int32_t)sizeof(DQuad);
-  in.device_bytes = (int64_t)s->block_bytes;
-  in.features = d.features;
+  in.bvh_depth = s->bvh_depth;
+  in.device_bytes = (int64_t)(s->block_bytes + (s->own_nodes ? s->node_room : 0));
   in.lds_nodes = d.n_lds_nodes;
   in.bvh_builder = builder;
-  in.bvh_arity = H.bvh_arity;
   in.stack_depth = d.stack_depth;
   in.lds_fixed_bytes = plan.fixed_bytes;
   in.lds_block_budget = plan.block_budget;
@@ -577,7 +613,24 @@ static void fill_info(rt_scene *s, const rtx::HostScene &H, const RtkLdsPlan &pl
   in.lds_prims_persistent = d.lds_items_pc > 0;
   in.persistent_block_waves = d.pc_waves;
   in.lds_perlin = d.lds_perlin;
+}
+
+static void fill_info(rt_scene *s, const rtx::HostScene &H, const RtkLdsPlan &plan, int builder) {
+  const DScene &d = s->ds;
+  rt_scene_info &in = s->info;
+  std::memset(&in, 0, sizeof in);
+  in.n_leaf_refs = s->n_items; // leaves are item ranges
+  in.n_spheres = (int32_t)H.spheres.size();
+  in.n_quads = (int32_t)H.quads.size();
+  in.n_objects = (int32_t)(s->n_items + H.mitems.size());
+  in.n_light_leaves = (int32_t)H.lights.size();
+  in.node_bytes = (int32_t)(H.bvh_arity == 4 ? sizeof(DNode4) : sizeof(DNode));
+  in.sphere_bytes = (int32_t)sizeof(DSphere);
+  in.quad_bytes = (int32_t)sizeof(DQuad);
+  in.features = d.features;
+  in.bvh_arity = H.bvh_arity;
   in.lds_node_bytes = RT_LDS_NODE_BYTES(d.features);
+  fill_tree_info(s, plan, builder);
 }
 
 int rt_scene_create_tuned(const rt_scene_desc *desc, int32_t device, const rt_tuning *tuning,
@@ -597,10 +650,12 @@ int rt_scene_create_tuned(const rt_scene_desc *desc, int32_t device, const rt_tu
   rc = open_scene(device, tune, H, layout_block(H, want4), s);
   if (rc == RT_OK) rc = build_world_tree(s.get(), H, want4, builder);
   if (rc == RT_OK) rc = collapse_world_tree(s.get(), H, want4);
-  if (rc == RT_OK) rc = apply_residency(s.get(), H, plan);
   if (rc != RT_OK) return rc;
-  fill_info(s.get(), H, plan, builder);
   keep_movable(s.get(), desc, H);
+  Residency res;
+  if ((rc = plan_residency(s.get(), s->ds.n_nodes, s->bvh_depth, s->bvh_depth4, res)) != RT_OK) return rc;
+  commit_residency(s.get(), res, plan);
+  fill_info(s.get(), H, plan, builder);
   *out = s.release();
   return RT_OK;
 }
@@ -627,6 +682,8 @@ int rt_scene_destroy(rt_scene *s) {
   bury(s, s->list_order);
   bury(s, s->refit);
   bury(s, s->move_buf);
+  bury(s, s->rebuild);
+  bury(s, s->own_nodes);
   for (auto &o : s->order) bury(s, o.tile_cost); // the slot's one allocation
   bury(s, s->block);
   if (s->last) (void)hipEventDestroy(s->last);
@@ -1336,7 +1393,8 @@ static int ensure_refit(rt_scene *s, hipStream_t st) {
   add(sizeof(int32_t) * n_obj); // sphere_of, at 0
   s->refit_named = add(sizeof(unsigned) * n_obj);
   s->refit_boxes = add(tree ? 6 * sizeof(double) * (size_t)s->n_items : 0);
-  s->refit_temp_bytes = tree ? rtk_refit_temp_bytes(s->n_items, d.n_nodes) : 0;
+  // room for any tree over these items (a rebuild's may have more nodes than creation's)
+  s->refit_temp_bytes = tree ? rtk_refit_temp_bytes(s->n_items, std::max(d.n_nodes, s->n_items - 1)) : 0;
   s->refit_temp = add(s->refit_temp_bytes);
   char *buf = nullptr;
   hipError_t e = scene_alloc(s, (void **)&buf, bytes);
@@ -1435,6 +1493,129 @@ int rt_scene_move_spheres_device(rt_scene *s, int32_t n, const int32_t *device_o
   if (!device_object_ids || !device_centres) return set_err(RT_ERR_INVALID, "null argument");
   DeviceGuard g(s->device);
   return move_on_stream(s, n, device_object_ids, device_centres, (hipStream_t)hip_stream);
+}
+
+// ---------------------------------------------------------------- rebuilding the world tree
+// The state of the scene's first rebuild: one allocation (rt_scene::Rebuild),
+// the compile-order items uploaded into it; the host's copy is let go.
+static int ensure_rebuild(rt_scene *s) {
+  if (s->rebuild) return RT_OK;
+  const size_t n = (size_t)s->n_items;
+  const bool wide = s->bvh_arity == 4;
+  rt_scene::Rebuild R;
+  size_t bytes = 0;
+  auto add = [&](size_t b) {
+    const size_t off = bytes;
+    bytes += align256(b ? b : 1);
+    return off;
+  };
+  R.items = add(sizeof(DItem) * n);
+  R.boxes = add(6 * sizeof(double) * n);
+  R.nodes = add(sizeof(DNode) * (n - 1));
+  R.nodes4 = add(wide ? sizeof(DNode4) * (n - 1) : 0);
+  R.sorted = add(sizeof(DItem) * n);
+  R.temp_bytes = std::max(rtk_sah_temp_bytes((int)n), wide ? rtk_collapse4_temp_bytes((int)n - 1) : (size_t)0);
+  R.temp = add(R.temp_bytes);
+  char *buf = nullptr;
+  hipError_t e = scene_alloc(s, (void **)&buf, bytes);
+  if (e != hipSuccess) return set_err(RT_ERR_OOM, std::string("hipMallocFromPoolAsync rebuild: ") + hipGetErrorString(e));
+  e = upload(s, buf + R.items, s->compile_items.data(), sizeof(DItem) * n, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    scene_free(s, buf);
+    return hip_err(e, "rebuild upload");
+  }
+  std::vector<DItem>().swap(s->compile_items);
+  s->rb = R;
+  s->rebuild = buf;
+  return RT_OK;
+}
+
+int rt_scene_rebuild_bvh(rt_scene *s, int32_t *rebuilt) {
+  if (rebuilt) *rebuilt = 0;
+  if (!s) return set_err(RT_ERR_INVALID, "null scene");
+  DScene &d = s->ds;
+  if (d.root_is_leaf || d.n_nodes <= 0 || s->n_items < 2) return RT_OK; // a flat world: nothing to rebuild
+  DeviceGuard g(s->device);
+  wait_scene(s); // synchronous: the scene's launch chain has ended, on whichever streams it ran
+  if (int rc = ensure_rebuild(s)) return rc;
+  const int n = s->n_items;
+  const bool wide = s->bvh_arity == 4;
+  const rt_scene::Rebuild &R = s->rb;
+  const DItem *items0 = (const DItem *)(s->rebuild + R.items);
+  double *boxes = (double *)(s->rebuild + R.boxes);
+  DNode *nodes = (DNode *)(s->rebuild + R.nodes);
+  DNode4 *nodes4 = (DNode4 *)(s->rebuild + R.nodes4);
+  DItem *sorted = (DItem *)(s->rebuild + R.sorted);
+  void *temp = s->rebuild + R.temp;
+  hipStream_t st = s->stream;
+  auto failed = [&](hipError_t e, const char *what) {
+    (void)hipStreamSynchronize(st); // nothing may still use the staging
+    return hip_err(e, what);
+  };
+  // 1-3: the tree a fresh RT_BVH_DEVICE_SAH scene at these positions gets, into staging
+  DeviceTree tree;
+  hipError_t e = rtk_item_boxes(items0, n, d.spheres, d.quads, d.xforms, boxes, st);
+  if (e == hipSuccess)
+    e = rtk_build_sah(boxes, items0, n, nodes, sorted, temp, R.temp_bytes, sah_stack_budget(s->tune), &tree.n_nodes,
+                      &tree.depth, &tree.root_leaf, st);
+  if (e != hipSuccess) return failed(e, "rebuild: device BVH build");
+  // 4: accept, or keep the refitted tree.  The instance (RT_FEAT_FLAT, the DRoot table) and the
+  // arity are creation's: a root leaf, a tree deeper than the stack or than the 4-wide verdict
+  // allows, or one the residency plan refuses is not taken
+  const int max_depth = s->tune.lbvh_max_depth > 0 ? (int)s->tune.lbvh_max_depth : RT_STACK_DEPTH - 1;
+  if (tree.root_leaf > 0 || tree.n_nodes < 1 || tree.depth < 0 || tree.depth > max_depth) return RT_OK;
+  int n4 = 0, d4 = 0;
+  double cost = s->binary_cost;
+  if (wide) {
+    e = rtk_collapse4(nodes, tree.n_nodes, nodes4, temp, R.temp_bytes, &n4, &d4, st);
+    KernelAttrs a4;
+    if (e == hipSuccess) e = rtk_instance_attrs(d.features, 0, &a4);
+    if (e != hipSuccess) return failed(e, "rebuild: 4-wide collapse");
+    if (collapse4_verdict(a4, d.features & ~RT_FEAT_BVH4, d4, s->tune.lds_cap) != COLLAPSE4_FITS) return RT_OK;
+    // rt_scene_bvh_cost's figure, with a fresh scene's bits: the host's sum over the binary tree
+    std::vector<DNode> host(tree.n_nodes);
+    e = upload(s, host.data(), nodes, sizeof(DNode) * host.size(), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return failed(e, "rebuild: BVH download");
+    cost = rtx::bvh_sah_cost(host);
+  }
+  const int n_new = wide ? n4 : tree.n_nodes;
+  Residency res;
+  if (plan_residency(s, n_new, tree.depth, d4, res) != RT_OK) return RT_OK;
+  // a host-built scene's node range holds its creation tree: one for any tree over these items
+  const size_t each = wide ? sizeof(DNode4) : sizeof(DNode);
+  char *range = (char *)const_cast<DNode *>(d.nodes), *fresh_range = nullptr;
+  if (each * (size_t)n_new > s->node_room) {
+    e = scene_alloc(s, (void **)&fresh_range, each * (size_t)(n - 1));
+    if (e != hipSuccess) return set_err(RT_ERR_OOM, std::string("hipMallocFromPoolAsync nodes: ") + hipGetErrorString(e));
+    range = fresh_range;
+  }
+  // 5: commit.  Up to here nothing live was written
+  e = hipMemcpyAsync(range, wide ? (const void *)nodes4 : (const void *)nodes, each * (size_t)n_new,
+                     hipMemcpyDeviceToDevice, st);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(const_cast<DItem *>(d.items), sorted, sizeof(DItem) * (size_t)n, hipMemcpyDeviceToDevice, st);
+  if (e == hipSuccess && s->refit) // a later first move builds them itself (ensure_refit)
+    e = rtk_refit_links(range, s->bvh_arity, n_new, s->refit + s->refit_temp, s->refit_temp_bytes, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(st);
+    scene_free(s, fresh_range);
+    return hip_err(e, "rebuild: commit");
+  }
+  if (fresh_range) {
+    s->own_nodes = fresh_range; // (a second one never happens: this one holds the bound)
+    s->node_room = each * (size_t)(n - 1);
+    d.nodes = (const DNode *)fresh_range;
+  }
+  d.n_nodes = n_new;
+  s->bvh_depth = tree.depth;
+  s->bvh_depth4 = d4;
+  if (wide) s->binary_cost = cost;
+  RtkLdsPlan plan{};
+  commit_residency(s, res, plan);
+  fill_tree_info(s, plan, RT_BVH_DEVICE_SAH);
+  if (rebuilt) *rebuilt = 1;
+  return RT_OK;
 }
 
 int rt_last_kernel_ms(rt_scene *s, double *ms) {
@@ -1708,6 +1889,20 @@ int rt_multi_move_spheres(rt_multi *m, int32_t n, const int32_t *object_ids, con
   // the shards hold one description: what the first refuses none has applied
   for (rt_scene *s : m->scenes)
     if (int rc = rt_scene_move_spheres(s, n, object_ids, centres)) return rc;
+  return RT_OK;
+}
+
+int rt_multi_rebuild_bvh(rt_multi *m, int32_t *rebuilt) {
+  if (rebuilt) *rebuilt = 0;
+  if (!m) return set_err(RT_ERR_INVALID, "null argument");
+  // the shards hold one description and one tuning: they decide alike
+  int32_t all = 1;
+  for (rt_scene *s : m->scenes) {
+    int32_t one = 0;
+    if (int rc = rt_scene_rebuild_bvh(s, &one)) return rc;
+    all &= one;
+  }
+  if (rebuilt) *rebuilt = m->scenes.empty() ? 0 : all;
   return RT_OK;
 }
 

@@ -1,6 +1,6 @@
 // rt_kernels.h — every rtk_* launcher, declared once: included by the files
 // that define them (rt_kernel.hip, rt_frame.hip, rt_adaptive.hip, rt_guides.hip,
-// rt_denoise.hip, rt_temporal.hip, rt_bvh_build.hip, rt_bvh_sah.hip, rt_refit.hip) and by their caller (rt_api.cpp), so a
+// rt_denoise.hip, rt_temporal.hip, rt_bvh_build.hip, rt_bvh_sah.hip, rt_collapse.hip, rt_refit.hip) and by their caller (rt_api.cpp), so a
 // definition whose parameter list drifts from its callers' no longer compiles.
 #ifndef RT_KERNELS_H
 #define RT_KERNELS_H
@@ -112,6 +112,15 @@ size_t rtk_sah_temp_bytes(int n);
 hipError_t rtk_build_sah(const double *boxes, const DItem *items_in, int n, DNode *nodes, DItem *items_out,
                          void *temp, size_t temp_bytes, int stack_budget, int *n_nodes, int *depth,
                          int *root_leaf, hipStream_t st);
+
+// ---- rt_collapse.hip: the binary tree `bin` (n_nodes records, root 0, any order) collapsed to
+// 4-wide nodes in BFS order, the bytes of rt_scene.cpp's collapse_bvh4 (rt_collapse.h is the source
+// of both).  out: room for n_nodes records, the first *n_nodes4 written; *levels: the 4-wide levels.
+// n_nodes < 1, a short temp and buffers that overlap are refused before anything is queued.
+// Synchronises `st` once per level; the tree is complete on return.
+size_t rtk_collapse4_temp_bytes(int n_nodes);
+hipError_t rtk_collapse4(const DNode *bin, int n_nodes, DNode4 *out, void *temp, size_t temp_bytes, int *n_nodes4,
+                         int *levels, hipStream_t st);
 
 // ---- rt_refit.hip: moved spheres and the bottom-up refit of the world tree's boxes.
 // nodes: DNode (arity 2) or DNode4 (arity 4) records.  temp (rtk_refit_temp_bytes) holds the

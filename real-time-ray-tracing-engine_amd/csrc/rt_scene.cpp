@@ -15,6 +15,7 @@
 // (BVHNode.cpp:21-123) and each leaf carries the product of the 1/2 and 1/N
 // weights above it.
 #include "rt_scene.h"
+#include "rt_collapse.h"
 #include "rt_plan.h"
 
 #include <algorithm>
@@ -281,6 +282,7 @@ struct SahBuilder {
     leaf_order.reserve(r.size());
     for (auto &x : r) leaf_order.push_back(H.items[x.obj]);
     H.items.swap(leaf_order);
+    H.compile_items.swap(leaf_order); // the order a device build starts from (rt_scene_rebuild_bvh)
     if (bn[root].left < 0) {
       H.root_is_leaf = 1;
       H.n_root_items = bn[root].count;
@@ -1062,64 +1064,19 @@ double bvh_sah_cost(const std::vector<DNode> &nodes) {
 int collapse_bvh4(const std::vector<DNode> &bin, std::vector<DNode4> &out) {
   out.clear();
   if (bin.empty()) return 0;
-  struct Child {
-    float lo[3], hi[3];
-    int32_t e;
-  };
-  auto child = [&](const DNode &b, int k) {
-    Child c;
-    for (int a = 0; a < 3; ++a) {
-      c.lo[a] = b.lo[a][k];
-      c.hi[a] = b.hi[a][k];
-    }
-    c.e = b.entry[k];
-    return c;
-  };
-  auto area = [](const Child &c) {
-    const double x = (double)c.hi[0] - c.lo[0], y = (double)c.hi[1] - c.lo[1],
-                 z = (double)c.hi[2] - c.lo[2];
-    return x * y + y * z + z * x;
-  };
+  const int n_bin = (int)bin.size();
   std::vector<int> src{0}, level{1}; // binary root and level of each 4-wide node
   int depth = 0;
   for (size_t k = 0; k < src.size(); ++k) {
-    const DNode &b = bin[src[k]];
-    Child c[4];
-    int n = 2;
-    c[0] = child(b, 0);
-    c[1] = child(b, 1);
-    while (n < 4) {
-      int pick = -1;
-      double best = -1.0;
-      for (int i = 0; i < n; ++i)
-        if (c[i].e >= 0 && area(c[i]) > best) {
-          best = area(c[i]);
-          pick = i;
-        }
-      if (pick < 0) break;
-      const DNode &m = bin[c[pick].e];
-      for (int i = n; i > pick + 1; --i) c[i] = c[i - 1]; // keep the leaf order
-      c[pick] = child(m, 0);
-      c[pick + 1] = child(m, 1);
-      ++n;
-    }
-    DNode4 q;
-    std::memset(&q, 0, sizeof q);
-    for (int i = 0; i < 4; ++i) {
-      for (int a = 0; a < 3; ++a) {
-        q.lo[a][i] = i < n ? c[i].lo[a] : std::numeric_limits<float>::infinity();
-        q.hi[a][i] = i < n ? c[i].hi[a] : -std::numeric_limits<float>::infinity();
-      }
-      if (i >= n) {
-        q.entry[i] = -1;
-      } else if (c[i].e >= 0) {
-        q.entry[i] = (int32_t)src.size();
-        src.push_back(c[i].e);
+    rt_collapse::Child c[4];
+    rt_collapse::expand(bin.data(), n_bin, src[k], c); // rt_collapse.h: the device collapse's too
+    DNode4 q = rt_collapse::node_of(c);
+    for (int i = 0; i < 4; ++i)
+      if (rt_collapse::is_inner(q.entry[i], n_bin)) { // BFS numbering: level by level, parent order, slot order
+        src.push_back(q.entry[i]);
+        q.entry[i] = (int32_t)src.size() - 1;
         level.push_back(level[k] + 1);
-      } else {
-        q.entry[i] = c[i].e;
       }
-    }
     depth = std::max(depth, level[k]);
     out.push_back(q);
   }

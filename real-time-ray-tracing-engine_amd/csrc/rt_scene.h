@@ -13,6 +13,10 @@ struct HostScene {
   std::vector<DNode> nodes;
   std::vector<DNode4> nodes4; // the world BVH collapsed to 4-wide nodes (bvh_arity 4)
   std::vector<DItem> items;
+  // the world items in compile order -- the order compile_scene emits them in,
+  // which a device build starts from -- once the host builder has put `items`
+  // into leaf order; empty while `items` is still in that order itself
+  std::vector<DItem> compile_items;
   std::vector<DItem> mitems; // media (not in the BVH)
   std::vector<float> mbox;   // 6 per medium
   std::vector<DItem> bitems;

@@ -258,4 +258,5 @@ EXPORTS = (
     "rt_history_variance_bytes", "rt_temporal_variance_device", "rt_denoise_given_variance_device",
     "rt_guided_select_device",
     "rt_scene_move_spheres", "rt_scene_move_spheres_device", "rt_multi_move_spheres",
+    "rt_scene_rebuild_bvh", "rt_multi_rebuild_bvh",
 )

@@ -98,6 +98,8 @@ def load():
     L.rt_scene_move_spheres.argtypes = [C.c_void_p, C.c_int32, P(C.c_int32), P(C.c_double)]
     L.rt_scene_move_spheres_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.rt_multi_move_spheres.argtypes = [C.c_void_p, C.c_int32, P(C.c_int32), P(C.c_double)]
+    L.rt_scene_rebuild_bvh.argtypes = [C.c_void_p, P(C.c_int32)]
+    L.rt_multi_rebuild_bvh.argtypes = [C.c_void_p, P(C.c_int32)]
     for name in abi.EXPORTS:
         getattr(L, name).restype = C.c_char_p if name == "rt_last_error" else C.c_int
     if L.rt_abi_version() != abi.RT_ABI_VERSION:

@@ -198,6 +198,16 @@ class Renderer:
         check(self.lib.rt_scene_move_spheres_device(self.handle, int(n), C.c_void_p(ids_ptr),
                                                     C.c_void_p(centres_ptr), C.c_void_p(stream_ptr or 0)))
 
+    def rebuild_bvh(self):
+        """rt_scene_rebuild_bvh: a new world BVH over the spheres where they
+        are now, built on the device -- the tree, info() and bvh_cost() of a
+        Renderer freshly made from the moved description with the device SAH
+        builder.  Synchronous.  True when the new tree was taken; False when
+        the scene keeps its refitted tree (a flat world, a tree too deep)."""
+        took = C.c_int32(0)
+        check(self.lib.rt_scene_rebuild_bvh(self.handle, C.byref(took)))
+        return bool(took.value)
+
 
 class MultiRenderer:
     """rt_multi_*: one device scene per shard (shard k on devices[k % len]),
@@ -245,6 +255,13 @@ class MultiRenderer:
         check(self.lib.rt_multi_move_spheres(self.handle, len(ids), ids.ctypes.data_as(C.POINTER(C.c_int32)),
                                              centres.ctypes.data_as(C.POINTER(C.c_double))))
         describe_move(self.scene_desc, ids, centres)
+
+    def rebuild_bvh(self):
+        """rt_multi_rebuild_bvh: Renderer.rebuild_bvh on every shard's scene;
+        True only if every shard took its new tree."""
+        took = C.c_int32(0)
+        check(self.lib.rt_multi_rebuild_bvh(self.handle, C.byref(took)))
+        return bool(took.value)
 
     def shard_ms(self):
         ms = (C.c_double * self.n_shards)()

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""Moving spheres measured.
+"""Moving spheres and the rebuild measured.
 
-    python tools/refit_bench.py [--sizes 486 100000 1000000] [--reps 20] [--log profiles/refit_bench.log]
+    python tools/refit_bench.py [--sizes 486 100000 1000000] [--reps 20] [--log profiles/rebuild_bench.log]
 
 Per size -- 486: bouncing_seed42 (bench.py's C3 scene, host tree, binary);
 otherwise that many random spheres in [-50, 50]^3 over a ground sphere
@@ -13,12 +13,25 @@ a 4-wide tree) -- one JSON line each for
             between HIP events; recreate_ms: rt_scene_destroy + rt_scene_create
             of the same description, host clock, the best of 3 (the host
             compile, the upload and the BVH build a move replaces);
+            rebuild_ms: one rt_scene_rebuild_bvh of a second scene of the same
+            description, host clock, the best of 3 after the first (which
+            allocates the rebuild state: first_rebuild_ms); cost_ms, for a
+            4-wide scene: rt_scene_bvh_cost of the same world created binary,
+            host clock -- the download of the binary tree and the host's sum
+            that a 4-wide rebuild contains for its binary_cost;
   walk      after 1, 10 and 100 steps of a random walk (every step adds a vector
             uniform in [-step, step]^3 to every moved sphere; step is stated in
             the line): frame_ms of one-stratum 1080p frames (HIP events, the
             mean of `reps`) and rt_scene_bvh_cost of the refitted scene, beside
             the same of a scene freshly created at those positions, and the
-            largest pixel difference between the two scenes' frames.
+            largest pixel difference between the two scenes' frames; and of
+            a second scene that made the same moves and then one
+            rt_scene_rebuild_bvh (rebuilt_frame_ms, rebuilt_bvh_cost, that
+            rebuild's host ms, and its largest pixel difference from the fresh
+            scene: 0 where the fresh scene is the device SAH builder's);
+  every_k   §7j's break-even arithmetic at each of those step counts: the
+            frame time the refitted tree loses against the rebuilt one, and
+            the frames after which a rebuild, or destroy + create, is repaid.
             rt_scene_bvh_cost of a 4-wide scene is creation's figure (rt_api.h):
             there only frame_ms shows the refitted tree's quality.
 
@@ -100,7 +113,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--sizes", type=int, nargs="+", default=[486, 100000, 1000000])
     ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--log", default=os.path.join(ROOT, "profiles", "refit_bench.log"))
+    ap.add_argument("--log", default=os.path.join(ROOT, "profiles", "rebuild_bench.log"))
     args = ap.parse_args()
     import torch
     from rtx import abi
@@ -142,8 +155,27 @@ def main():
             move(d_home)
         t1.record(stream)
         t1.synchronize()
-        say(kind="move", n=n, **tree, move_ms=t0.elapsed_time(t1) / args.reps, recreate_ms=min(create_ms[1:]),
-            first_create_with_python_ms=create_ms[0])
+        # the rebuild, on a scene of its own: R keeps creation's topology for the walk
+        R2 = Renderer(S)
+        rebuild_ms = []
+        for _ in range(4):
+            t = time.perf_counter()
+            took = R2.rebuild_bvh()
+            rebuild_ms.append((time.perf_counter() - t) * 1e3)
+        cost_ms = None
+        if info["bvh_arity"] == 4:
+            arity, S.bvh_arity = S.bvh_arity, 2
+            with Renderer(S) as R3:
+                cost_ms = []
+                for _ in range(3):
+                    t = time.perf_counter()
+                    R3.bvh_cost()
+                    cost_ms.append((time.perf_counter() - t) * 1e3)
+            S.bvh_arity, cost_ms = arity, min(cost_ms)
+        recreate_ms = min(create_ms[1:])
+        say(kind="move", n=n, **tree, move_ms=t0.elapsed_time(t1) / args.reps, recreate_ms=recreate_ms,
+            first_create_with_python_ms=create_ms[0], rebuilt=took, rebuild_ms=min(rebuild_ms[1:]),
+            first_rebuild_ms=rebuild_ms[0], cost_ms=cost_ms, rebuilt_nodes=R2.info()["n_nodes"])
         ms0, _ = frame_ms(torch, R, frame, buf, args.reps)
         say(kind="walk", n=n, steps=0, step=step, frame_ms=ms0, bvh_cost=R.bvh_cost())
         rng = np.random.default_rng(9)
@@ -153,6 +185,7 @@ def main():
                 at = at + rng.uniform(-step, step, size=at.shape)
                 d_at = torch.from_numpy(at).cuda()
                 move(d_at)
+                R2.move_spheres_device(d_ids.data_ptr(), d_at.data_ptr(), len(ids), stream.cuda_stream)
                 done += 1
             torch.cuda.synchronize()
             ms, img = frame_ms(torch, R, frame, buf, args.reps)
@@ -161,8 +194,19 @@ def main():
             with Renderer(S) as F:
                 fms, fimg = frame_ms(torch, F, frame, buf, args.reps)
                 fcost = F.bvh_cost()
+            t = time.perf_counter()
+            took = R2.rebuild_bvh()
+            walk_rebuild_ms = (time.perf_counter() - t) * 1e3
+            rms, rimg = frame_ms(torch, R2, frame, buf, args.reps)
             say(kind="walk", n=n, steps=upto, step=step, frame_ms=ms, fresh_frame_ms=fms, slowdown=ms / fms,
-                bvh_cost=cost, fresh_bvh_cost=fcost, max_pixel_diff=float(np.nanmax(np.abs(img - fimg))))
+                bvh_cost=cost, fresh_bvh_cost=fcost, max_pixel_diff=float(np.nanmax(np.abs(img - fimg))),
+                rebuilt=took, rebuild_ms=walk_rebuild_ms, rebuilt_frame_ms=rms, rebuilt_bvh_cost=R2.bvh_cost(),
+                rebuilt_max_pixel_diff=float(np.nanmax(np.abs(rimg - fimg))))
+            lost = ms - rms
+            say(kind="every_k", n=n, k=upto, lost_ms_per_frame=lost, rebuild_ms=walk_rebuild_ms,
+                recreate_ms=recreate_ms, frames_to_repay_rebuild=walk_rebuild_ms / lost if lost > 0 else None,
+                frames_to_repay_recreate=recreate_ms / lost if lost > 0 else None)
+        R2.close()
         R.close()
     LOG.close()
 
