@@ -10,7 +10,9 @@
 //    the wave stays full until the tile's queue drains instead of idling lanes
 //    whose pixels finished early (sky pixels vs multi-bounce pixels);
 //  * the recursive integrator becomes an iterative bounce loop carrying a
-//    throughput; every lane traces exactly one segment per loop trip;
+//    throughput; every lane traces exactly one segment per loop trip (in the
+//    plain flat world a lane that hit waits, parked, until enough lanes of its
+//    wave have a hit to shade: RT_PARK_MIN);
 //  * stateless Philox4x32-10 random numbers keyed by (seed; pixel, stratum,
 //    bounce, slot) — no per-pixel curandState traffic (48 B/pixel/sample in the
 //    reference) and sample ranges shard across GPUs exactly;
@@ -45,7 +47,20 @@ namespace {
 using namespace rtp;
 // Idle lanes that trigger a refill while other lanes still trace (measured:
 // 16 for the plain instance, C3 +4 %; the rich instances lose with any delay).
-#define RT_REGEN_MIN(F) ((F) == F_FLAT ? 16 : (((F) & ~F_BVH4) == 0 ? 16 : 1))
+#ifndef RT_REGEN_FLAT
+#define RT_REGEN_FLAT 16 // re-measured with RT_PARK_K (profiles/parked_k_ab.log)
+#endif
+#define RT_REGEN_MIN(F) ((F) == F_FLAT ? RT_REGEN_FLAT : (((F) & ~F_BVH4) == 0 ? 16 : 1))
+// Parked shading (the plain flat world, every instance of it: M_ANY, M_DIFFUSE,
+// STATS, COST): a lane whose trace hit keeps (closest, best) and is shaded only
+// once this many lanes of its wave hold a hit, or no refill can add to them --
+// shade, the dearest block of a trip, then runs once for the few bounce rays
+// that hit and the camera rays of the next refill together.  0: trace and shade
+// in one step (segment).  Measured on C2: DESIGN.md §7, profiles/parked_*.
+#ifndef RT_PARK_K
+#define RT_PARK_K 48
+#endif
+#define RT_PARK_MIN(F) ((F) == F_FLAT ? RT_PARK_K : 0)
 // Occupancy target per instance (waves per SIMD): the compiler may spill a few
 // registers to reach it.  Measured: 4 for the plain instance (C3
 // +12 % over 3), 3 for the rich ones (C4 +8.6 % over the 2 that 224 VGPRs give).
@@ -364,6 +379,10 @@ __global__ __launch_bounds__(64 * (PCW ? PCW : block_waves(F))) __attribute__((a
   PathState ps;
   ps.active = false;
   Key key{P.seed_lo, P.seed_hi, 0, 0};
+  // a parked lane's hit (RT_PARK_MIN): pk_best >= 0 is the flag
+  constexpr int kPark = RT_PARK_MIN(F);
+  [[maybe_unused]] double pk_closest = 0.0;
+  [[maybe_unused]] int pk_best = -1;
 
   for (;;) {
     // ---- regeneration: idle lanes pull the next (pixel, stratum) items
@@ -395,10 +414,47 @@ __global__ __launch_bounds__(64 * (PCW ? PCW : block_waves(F))) __attribute__((a
       }
     }
     if (STATS) cyc_regen += clk() - t_regen; // converged here (every lane)
-    if (__ballot(ps.active) == 0) break;
+    if (__ballot(ps.active) == 0) break; // a parked lane is active
     if (STATS) n_trips++; // converged here: every lane counts, lane 0 reports
     uint32_t v_trace = 0;
-    if (ps.active) {
+    if constexpr (kPark > 0) {
+      // ---- parked shading (RT_PARK_MIN): trace, and shade only once enough
+      // lanes hold a hit or no refill can add to them
+      bool done = false; // this lane's path ended in this trip: ps.T is its sample
+      if (ps.active && pk_best < 0) {
+        if (STATS) n_segments++;
+        const uint64_t t0 = STATS ? clk() : 0;
+        trace_closest<STATS, F, PC>(S, ps.ray, pk_closest, pk_best, stk, lnodes, cnt,
+                                    (RT_LDS LeafPool *)&leaf_pool[0], lp);
+        if (STATS && wave_once()) cnt.ctrace += clk() - t0;
+        if (pk_best < 0) { // miss -> background (Camera.cpp:242-243)
+          ps.T = ps.T * ld3(C.bg);
+          done = true;
+        }
+      }
+      const bool parked = ps.active && pk_best >= 0;
+      // Wave-uniform.  Shading waits only while the next trip's regeneration is
+      // certain to take items: with next_item < n_items and at least
+      // RT_REGEN_MIN idle lanes (a lane that just missed is idle once it has
+      // added its sample below) the refill rule above passes both of its
+      // breaks, and next_item grows by the idle count.  n_items is finite, so
+      // after finitely many such trips next_item reaches it, `wait` is false
+      // and every parked lane is shaded: the loop cannot spin.
+      const bool wait = __popcll(__ballot(parked)) < kPark && next_item < n_items &&
+                        __popcll(__ballot(!ps.active || done)) >= RT_REGEN_MIN(F);
+      if (!wait && parked) { // ---- the one shade site
+        const uint64_t t1 = STATS ? clk() : 0;
+        done = !shade_closest<STATS, F, PC, MS>(S, C, ps, key, pk_closest, pk_best, cnt, lp);
+        if (STATS && wave_once()) cnt.cshade += clk() - t1;
+        pk_best = -1;
+      }
+      if (done) {
+        atomicAdd(&acc[ps.slot * 3 + 0], ps.T.x);
+        atomicAdd(&acc[ps.slot * 3 + 1], ps.T.y);
+        atomicAdd(&acc[ps.slot * 3 + 2], ps.T.z);
+        ps.active = false;
+      }
+    } else if (ps.active) {
       if (STATS) n_segments++;
       const uint32_t nv0 = cnt.nodes;
       bool cont = segment<STATS, F, PC, MS>(

@@ -1559,11 +1559,15 @@ RT_HD RT_FI bool trace_tail(const DScene &S, const Ray &r, Hit &h, const Key &ke
 // `lnodes` is the LDS copy of nodes [0, S.n_lds_nodes): DNode4 for 4-wide trees,
 // DNodeL for binary ones (the host emulator passes the same forms
 // of the whole tree).
-template <bool STATS, unsigned F, bool LP = false>
+// ROOTS: the search alone -- the closest primitive root and its world item
+// (-1: none) go to *closest_out / *best_out, before media and without the
+// record (h, key and bounce are not read); trace_closest below is that form.
+template <bool STATS, unsigned F, bool LP = false, bool ROOTS = false>
 RT_HD RT_FI bool trace(const DScene &S, const Ray &r, Hit &h, const Key &key,
                                       uint32_t bounce, int *stk, const RT_LDS DNode *lnodes,
                                       Counters &cnt, RT_LDS LeafPool *pool = nullptr,
-                                      const LdsPrims &lp = LdsPrims{}) {
+                                      const LdsPrims &lp = LdsPrims{}, double *closest_out = nullptr,
+                                      int *best_out = nullptr) {
   const double tmin = 0.001; // Camera.cpp:242
   double closest = kInf;
   int best = -1;
@@ -1984,7 +1988,23 @@ RT_HD RT_FI bool trace(const DScene &S, const Ray &r, Hit &h, const Key &key,
       }
     }
   }
-  return trace_tail<STATS, F, LP>(S, r, h, key, bounce, closest, best, cnt, lp);
+  if constexpr (ROOTS) {
+    *closest_out = closest;
+    *best_out = best;
+    return best >= 0;
+  } else {
+    return trace_tail<STATS, F, LP>(S, r, h, key, bounce, closest, best, cnt, lp);
+  }
+}
+// The search half of trace on its own, for the flat render loop, which calls
+// the two halves apart (shade_closest below) so that a lane can hold
+// (closest, best) for a while.
+template <bool STATS, unsigned F, bool LP = false>
+RT_HD RT_FI void trace_closest(const DScene &S, const Ray &r, double &closest, int &best, int *stk,
+                               const RT_LDS DNode *lnodes, Counters &cnt,
+                               RT_LDS LeafPool *pool = nullptr, const LdsPrims &lp = LdsPrims{}) {
+  Hit h; // not touched
+  trace<STATS, F, LP, true>(S, r, h, Key{}, 0u, stk, lnodes, cnt, pool, lp, &closest, &best);
 }
 
 // ------------------------------------------------------------ lights
@@ -2338,6 +2358,21 @@ RT_HD RT_FI bool segment(const DScene &S, const DCamera &C, PathState &ps,
   const bool cont = shade<STATS, F, MS>(S, C, ps, key, h, cnt);
   if (STATS && wave_once()) cnt.cshade += clk() - t1;
   return cont;
+}
+
+// The second half of a segment on its own: the record of world item `best` at
+// root `closest` of ps.ray (trace_closest's result, best >= 0), then shade.
+// trace_tail and shade see what segment hands them, in the same order; what
+// may lie between the two halves is other lanes' work only (rt_kernel.hip,
+// RT_PARK_MIN).
+template <bool STATS, unsigned F, bool LP = false, MatSet MS = M_ANY>
+RT_HD RT_FI bool shade_closest(const DScene &S, const DCamera &C, PathState &ps, const Key &key,
+                               double closest, int best, Counters &cnt,
+                               const LdsPrims &lp = LdsPrims{}) {
+  static_assert((F & F_MEDIA) == 0, "a medium is hit or passed in trace_tail: no split with media");
+  Hit h;
+  trace_tail<STATS, F, LP>(S, ps.ray, h, key, ps.bounce, closest, best, cnt, lp);
+  return shade<STATS, F, MS>(S, C, ps, key, h, cnt);
 }
 
 // The camera ray of stratum k of pixel (i, j) from its slot-0 block jt
