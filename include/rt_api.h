@@ -58,6 +58,10 @@
  *                        (CudaSceneInitialization.cuh:249-300) and DynamicCamera moves only the
  *                        camera; these move world spheres of a live scene and refit the world
  *                        BVH's boxes on the device
+ *   rt_scene_set_transforms / rt_scene_move_quads (and their _device / rt_multi_ forms),
+ *   rt_rotate_y_sincos
+ *                     <- no counterpart, as above: these set translate / rotate_y objects and
+ *                        move quads of a live scene; media boxes and the world BVH follow
  *   rt_last_error     <- replaces CUDA_CHECK's exit() and the converters' exceptions
  *                        (CudaMemoryUtility.cuh:9-15, HittableConverter.cuh:103-108): errors are
  *                        returned as negative codes, never thrown or exit()ed across the ABI.
@@ -990,6 +994,80 @@ int rt_scene_rebuild_bvh(rt_scene *scene, int32_t *rebuilt);
 /* rt_scene_rebuild_bvh on every shard's scene; *rebuilt is 1 only if every
    shard took its new tree. */
 int rt_multi_rebuild_bvh(rt_multi *multi, int32_t *rebuilt);
+
+/* ---- live transforms and quads (functions added under ABI 5: no struct or
+   signature above changed) ---------------------------------------------------
+   The Cornell scenes are made of quads, of boxes placed by
+   translate(rotate_y(box)), of constant media bounded by such boxes and of a
+   quad lamp; these functions move them the way rt_scene_move_spheres moves
+   spheres: the new values go into the device tables, every constant medium's
+   world box is recomputed from its boundary, and the world tree is refitted
+   (csrc/rt_refit.hip; DESIGN.md "Live transforms and quads").  The edited
+   scene renders what a scene freshly created from the edited description
+   renders (same hits; the usual exact-t ties aside).  rt_scene_rebuild_bvh
+   works from the edited tables.  As after a sphere move, tile dispatch orders
+   are kept, and what the caller accumulated or displayed before the edit
+   describes the old scene: the caller resets it.
+
+   object_ids index rt_scene_desc.objects.
+
+   A RT_OBJ_TRANSLATE or RT_OBJ_ROTATE_Y object is settable when it stands in
+   the transform chain of a world primitive, of a world constant medium, of a
+   medium's boundary or of an entry of the lights list.  Every place the object
+   stands in follows.  values: n x 3 doubles; a translate gets its offset, a
+   rotate_y gets (sin, cos, ignored) -- the stored form of rt_object_desc
+   (moving == RT_STORED_FORM); rt_rotate_y_sincos gives the pair of an angle.
+   A medium's boundary constants do not depend on the transforms above the
+   boundary, so a transform inside or above a medium is settable like any other.
+
+   A RT_OBJ_QUAD object is movable when it is among the world's primitive items
+   or an entry of the lights list (under any chain), and does not bound a
+   constant medium.  A move sets the corner Q (rt_object_desc.a); the sides u
+   and v stay, and with them the normal and the area.  A lamp that is one quad
+   object in the world and another in the lights list is two objects: the
+   caller moves both. */
+
+/* Validates everything first, and on any error leaves the scene untouched: an
+   id out of range, an object that is not a translate or rotate_y, one that
+   stands in no chain, an id named twice or a value that is not finite is
+   RT_ERR_INVALID (the third value of a rotate_y row is not looked at).  n = 0
+   is a no-op.  Synchronous: waits for the scene's pending launches, and the
+   edit has completed on return. */
+int rt_scene_set_transforms(rt_scene *scene, int32_t n, const int32_t *object_ids, const double *values);
+
+/* The same with device arrays, asynchronously on hip_stream (NULL = the HIP
+   null stream), a link of the scene's launch chain like
+   rt_scene_move_spheres_device.  An entry the host variant would refuse is
+   skipped on the device (both entries of an id named twice); the others are
+   applied.  The scene's first edit or move also allocates its refit state. */
+int rt_scene_set_transforms_device(rt_scene *scene, int32_t n, const int32_t *device_object_ids,
+                                   const double *device_values, void *hip_stream);
+
+/* rt_scene_set_transforms on every shard's scene.  Host arrays only. */
+int rt_multi_set_transforms(rt_multi *multi, int32_t n, const int32_t *object_ids, const double *values);
+
+/* corners: n x 3 doubles.  Validates everything first, and on any error leaves
+   the scene untouched: an id out of range, an object that is not a quad, a
+   quad that is neither a world primitive item nor a light entry, an id named
+   twice, a corner that is not finite or whose plane constant dot(n, Q) is not
+   finite is RT_ERR_INVALID; a quad that bounds a constant medium is
+   RT_ERR_UNSUPPORTED (the medium's face constants would have to follow).
+   n = 0 is a no-op.  Synchronous, like rt_scene_set_transforms. */
+int rt_scene_move_quads(rt_scene *scene, int32_t n, const int32_t *object_ids, const double *corners);
+
+/* The same with device arrays, asynchronously on hip_stream; entries the host
+   variant would refuse are skipped. */
+int rt_scene_move_quads_device(rt_scene *scene, int32_t n, const int32_t *device_object_ids,
+                               const double *device_corners, void *hip_stream);
+
+/* rt_scene_move_quads on every shard's scene.  Host arrays only. */
+int rt_multi_move_quads(rt_multi *multi, int32_t n, const int32_t *object_ids, const double *corners);
+
+/* (sin, cos) of a rotate_y angle given in degrees, exactly as scene creation
+   computes them from rt_object_desc.s: the row rt_scene_set_transforms takes.
+   Needs no scene and no device.  RT_ERR_INVALID (no message is set): a null
+   pointer. */
+int rt_rotate_y_sincos(double degrees, double *sin_theta, double *cos_theta);
 
 /* ---- guided sampling (one function added under ABI 5: no struct or signature
    above changed) ------------------------------------------------------------

@@ -27,6 +27,7 @@
 #include "rt_layout.h"
 #include "rt_lds_plan.h"
 #include "rt_plan.h"
+#include "rt_live_check.h"
 #include "rt_scene.h"
 
 struct rt_scene {
@@ -95,6 +96,13 @@ struct rt_scene {
   int32_t n_items = 0, bvh_arity = 2;
   char *refit = nullptr;
   size_t refit_named = 0, refit_boxes = 0, refit_temp = 0, refit_temp_bytes = 0;
+  // Live transforms and quads (rt_scene_set_transforms*, rt_scene_move_quads*).  Kept from
+  // creation: the compiler's per-object index (HostScene::xf_kind, xf_first, xf_recs, quad_of)
+  // and each quad record's unit normal (3 doubles), which the host variants' checks read.
+  // `refit` holds the index's device copy at these offsets, `named` serves every kind of edit.
+  std::vector<int32_t> xf_kind, xf_first, xf_recs, quad_of;
+  std::vector<double> quad_n;
+  size_t refit_xf_kind = 0, refit_xf_first = 0, refit_xf_recs = 0, refit_quad_of = 0;
   char *move_buf = nullptr;
   size_t move_bytes = 0;
   // Rebuilding the world tree (rt_scene_rebuild_bvh).  Kept from creation: the
@@ -590,6 +598,13 @@ static void keep_movable(rt_scene *s, const rt_scene_desc *desc, rtx::HostScene 
     if (it.kind == I_SPHERE) s->sphere_of[it.id] = it.idx;
   for (const DItem &it : H.bitems)
     if (it.kind == I_SPHERE) s->sphere_of[it.id] = -2;
+  s->xf_kind = std::move(H.xf_kind);
+  s->xf_first = std::move(H.xf_first);
+  s->xf_recs = std::move(H.xf_recs);
+  s->quad_of = std::move(H.quad_of);
+  s->quad_n.resize(3 * H.quads.size());
+  for (size_t q = 0; q < H.quads.size(); ++q)
+    for (int a = 0; a < 3; ++a) s->quad_n[3 * q + a] = H.quads[q].n[a];
   // a host build left H.items in leaf order and handed the compile order over;
   // a device build sorted the device's copy only
   s->compile_items = std::move(H.compile_items.empty() ? H.items : H.compile_items);
@@ -1375,10 +1390,11 @@ int rt_scene_bvh_cost(const rt_scene *s, double *cost) {
   return RT_OK;
 }
 
-// ---------------------------------------------------------------- moving spheres
-// The state of the scene's first move: one allocation, the movable-sphere
-// table uploaded and the tree's links built on `st` (the move's stream; later
-// moves on other streams follow through the launch chain).
+// ---------------------------------------------------------------- moving spheres, live transforms and quads
+// The state of the scene's first move or edit: one allocation, the
+// movable-sphere table and the live index uploaded and the tree's links built
+// on `st` (the move's stream; later moves on other streams follow through the
+// launch chain).
 static int ensure_refit(rt_scene *s, hipStream_t st) {
   if (s->refit) return RT_OK;
   const DScene &d = s->ds;
@@ -1396,10 +1412,22 @@ static int ensure_refit(rt_scene *s, hipStream_t st) {
   // room for any tree over these items (a rebuild's may have more nodes than creation's)
   s->refit_temp_bytes = tree ? rtk_refit_temp_bytes(s->n_items, std::max(d.n_nodes, s->n_items - 1)) : 0;
   s->refit_temp = add(s->refit_temp_bytes);
+  s->refit_xf_kind = add(sizeof(int32_t) * s->xf_kind.size());
+  s->refit_xf_first = add(sizeof(int32_t) * s->xf_first.size());
+  s->refit_xf_recs = add(sizeof(int32_t) * s->xf_recs.size());
+  s->refit_quad_of = add(sizeof(int32_t) * s->quad_of.size());
   char *buf = nullptr;
   hipError_t e = scene_alloc(s, (void **)&buf, bytes);
   if (e != hipSuccess) return set_err(RT_ERR_OOM, std::string("hipMallocFromPoolAsync refit: ") + hipGetErrorString(e));
   e = hipMemcpyAsync(buf, s->sphere_of.data(), sizeof(int32_t) * n_obj, hipMemcpyHostToDevice, st);
+  auto put = [&](size_t off, const std::vector<int32_t> &v) {
+    if (e == hipSuccess && !v.empty())
+      e = hipMemcpyAsync(buf + off, v.data(), sizeof(int32_t) * v.size(), hipMemcpyHostToDevice, st);
+  };
+  put(s->refit_xf_kind, s->xf_kind);
+  put(s->refit_xf_first, s->xf_first);
+  put(s->refit_xf_recs, s->xf_recs);
+  put(s->refit_quad_of, s->quad_of);
   if (e == hipSuccess && tree)
     e = rtk_refit_links(d.nodes, s->bvh_arity, d.n_nodes, buf + s->refit_temp, s->refit_temp_bytes, st);
   if (e != hipSuccess) {
@@ -1411,25 +1439,66 @@ static int ensure_refit(rt_scene *s, hipStream_t st) {
   return RT_OK;
 }
 
-// One move on `st`, a link of the scene's launch chain: the centres, then
-// every world item's box from the tables and a full refit of the tree.
-static int move_on_stream(rt_scene *s, int32_t n, const int32_t *d_ids, const double *d_centres, hipStream_t st) {
+// One update on `st`, a link of the scene's launch chain: the values into the
+// tables (sphere centres, transform records or quad corners), then what follows
+// from the tables -- every medium's world box, every world item's box and a
+// full refit of the tree.  All three kinds of update share the tail.
+enum EditKind { EDIT_SPHERES, EDIT_TRANSFORMS, EDIT_QUADS };
+static const char *edit_name(EditKind k) {
+  return k == EDIT_SPHERES ? "move spheres" : k == EDIT_TRANSFORMS ? "set transforms" : "move quads";
+}
+static rt_live::LiveIndex device_index(const rt_scene *s) {
+  rt_live::LiveIndex L{};
+  L.n_objects = (int32_t)s->xf_kind.size();
+  L.xf_kind = (const int32_t *)(s->refit + s->refit_xf_kind);
+  L.xf_first = (const int32_t *)(s->refit + s->refit_xf_first);
+  L.xf_recs = (const int32_t *)(s->refit + s->refit_xf_recs);
+  L.quad_of = (const int32_t *)(s->refit + s->refit_quad_of);
+  return L;
+}
+static rt_live::LiveIndex host_index(const rt_scene *s) {
+  rt_live::LiveIndex L{};
+  L.n_objects = (int32_t)s->xf_kind.size();
+  L.xf_kind = s->xf_kind.data();
+  L.xf_first = s->xf_first.data();
+  L.xf_recs = s->xf_recs.data();
+  L.quad_of = s->quad_of.data();
+  return L;
+}
+static int edit_on_stream(rt_scene *s, EditKind kind, int32_t n, const int32_t *d_ids, const double *d_values,
+                          hipStream_t st) {
   int rc = order_after_last(s, st);
   if (rc) return rc;
   if ((rc = ensure_refit(s, st))) return rc;
   const DScene &d = s->ds;
-  RefitMove m{};
-  m.ids = d_ids;
-  m.centres = d_centres;
-  m.n = n;
-  m.n_objects = (int32_t)s->sphere_of.size();
-  m.sphere_of = (const int32_t *)s->refit;
-  m.named = (unsigned *)(s->refit + s->refit_named);
-  m.spheres = const_cast<DSphere *>(d.spheres);
-  m.roots = const_cast<DRoot *>(d.roots);
-  m.root_items = d.items;
-  m.n_roots = d.n_roots;
-  hipError_t e = rtk_move_spheres(&m, st);
+  hipError_t e;
+  if (kind == EDIT_SPHERES) {
+    RefitMove m{};
+    m.ids = d_ids;
+    m.centres = d_values;
+    m.n = n;
+    m.n_objects = (int32_t)s->sphere_of.size();
+    m.sphere_of = (const int32_t *)s->refit;
+    m.named = (unsigned *)(s->refit + s->refit_named);
+    m.spheres = const_cast<DSphere *>(d.spheres);
+    m.roots = const_cast<DRoot *>(d.roots);
+    m.root_items = d.items;
+    m.n_roots = d.n_roots;
+    e = rtk_move_spheres(&m, st);
+  } else {
+    LiveEdit le{};
+    le.ids = d_ids;
+    le.values = d_values;
+    le.n = n;
+    le.index = device_index(s);
+    le.named = (unsigned *)(s->refit + s->refit_named);
+    le.xforms = const_cast<DXform *>(d.xforms);
+    le.quads = const_cast<DQuad *>(d.quads);
+    e = kind == EDIT_TRANSFORMS ? rtk_set_transforms(&le, st) : rtk_move_quads(&le, st);
+  }
+  if (e == hipSuccess && d.n_mitems > 0) // a flat world has media too
+    e = rtk_medium_boxes(d.mitems, d.n_mitems, d.media, d.bitems, d.spheres, d.quads, d.xforms,
+                         const_cast<float *>(d.mbox), st);
   if (e == hipSuccess && !d.root_is_leaf && d.n_nodes > 0) {
     double *boxes = (double *)(s->refit + s->refit_boxes);
     e = rtk_item_boxes(d.items, s->n_items, d.spheres, d.quads, d.xforms, boxes, st);
@@ -1439,7 +1508,7 @@ static int move_on_stream(rt_scene *s, int32_t n, const int32_t *d_ids, const do
   }
   // whatever was queued reads and writes the scene's tables: the chain ends after it either way
   rc = mark_last(s, st);
-  if (e != hipSuccess) return hip_err(e, "move spheres");
+  if (e != hipSuccess) return hip_err(e, edit_name(kind));
   return rc;
 }
 
@@ -1462,11 +1531,21 @@ static int check_move(const rt_scene *s, int32_t n, const int32_t *ids, const do
   return RT_OK;
 }
 
-int rt_scene_move_spheres(rt_scene *s, int32_t n, const int32_t *object_ids, const double *centres) {
+static int check_edit(const rt_scene *s, EditKind kind, int32_t n, const int32_t *ids, const double *values) {
+  if (kind == EDIT_SPHERES) return check_move(s, n, ids, values);
+  std::string err;
+  const int rc = kind == EDIT_TRANSFORMS ? rt_live::check_transforms(host_index(s), n, ids, values, err)
+                                         : rt_live::check_quads(host_index(s), n, ids, values, s->quad_n.data(), err);
+  return rc == RT_OK ? RT_OK : set_err(rc, err);
+}
+
+// The host variants: everything validated, the arrays staged, one update on the
+// scene's own stream, complete on return.
+static int edit_from_host(rt_scene *s, EditKind kind, int32_t n, const int32_t *object_ids, const double *values) {
   if (!s || n < 0) return set_err(RT_ERR_INVALID, "null scene or negative count");
   if (n == 0) return RT_OK;
-  if (!object_ids || !centres) return set_err(RT_ERR_INVALID, "null argument");
-  int rc = check_move(s, n, object_ids, centres);
+  if (!object_ids || !values) return set_err(RT_ERR_INVALID, "null argument");
+  int rc = check_edit(s, kind, n, object_ids, values);
   if (rc) return rc;
   DeviceGuard g(s->device);
   const size_t id_bytes = align256(sizeof(int32_t) * (size_t)n), c_bytes = 3 * sizeof(double) * (size_t)n;
@@ -1475,24 +1554,49 @@ int rt_scene_move_spheres(rt_scene *s, int32_t n, const int32_t *object_ids, con
     return rc;
   hipError_t e = hipMemcpyAsync(s->move_buf, object_ids, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, s->stream);
   if (e == hipSuccess)
-    e = hipMemcpyAsync(s->move_buf + id_bytes, centres, c_bytes, hipMemcpyHostToDevice, s->stream);
+    e = hipMemcpyAsync(s->move_buf + id_bytes, values, c_bytes, hipMemcpyHostToDevice, s->stream);
   if (e != hipSuccess) {
     (void)hipStreamSynchronize(s->stream);
     return hip_err(e, "move upload");
   }
-  rc = move_on_stream(s, n, (const int32_t *)s->move_buf, (const double *)(s->move_buf + id_bytes), s->stream);
+  rc = edit_on_stream(s, kind, n, (const int32_t *)s->move_buf, (const double *)(s->move_buf + id_bytes), s->stream);
   e = hipStreamSynchronize(s->stream);
   if (rc) return rc;
-  return e == hipSuccess ? RT_OK : hip_err(e, "move spheres");
+  return e == hipSuccess ? RT_OK : hip_err(e, edit_name(kind));
 }
 
-int rt_scene_move_spheres_device(rt_scene *s, int32_t n, const int32_t *device_object_ids,
-                                 const double *device_centres, void *hip_stream) {
+// The device variants: asynchronous on the caller's stream.
+static int edit_from_device(rt_scene *s, EditKind kind, int32_t n, const int32_t *d_ids, const double *d_values,
+                            void *hip_stream) {
   if (!s || n < 0) return set_err(RT_ERR_INVALID, "null scene or negative count");
   if (n == 0) return RT_OK;
-  if (!device_object_ids || !device_centres) return set_err(RT_ERR_INVALID, "null argument");
+  if (!d_ids || !d_values) return set_err(RT_ERR_INVALID, "null argument");
   DeviceGuard g(s->device);
-  return move_on_stream(s, n, device_object_ids, device_centres, (hipStream_t)hip_stream);
+  return edit_on_stream(s, kind, n, d_ids, d_values, (hipStream_t)hip_stream);
+}
+
+int rt_scene_move_spheres(rt_scene *s, int32_t n, const int32_t *object_ids, const double *centres) {
+  return edit_from_host(s, EDIT_SPHERES, n, object_ids, centres);
+}
+int rt_scene_move_spheres_device(rt_scene *s, int32_t n, const int32_t *device_object_ids,
+                                 const double *device_centres, void *hip_stream) {
+  return edit_from_device(s, EDIT_SPHERES, n, device_object_ids, device_centres, hip_stream);
+}
+
+int rt_scene_set_transforms(rt_scene *s, int32_t n, const int32_t *object_ids, const double *values) {
+  return edit_from_host(s, EDIT_TRANSFORMS, n, object_ids, values);
+}
+int rt_scene_set_transforms_device(rt_scene *s, int32_t n, const int32_t *device_object_ids,
+                                   const double *device_values, void *hip_stream) {
+  return edit_from_device(s, EDIT_TRANSFORMS, n, device_object_ids, device_values, hip_stream);
+}
+
+int rt_scene_move_quads(rt_scene *s, int32_t n, const int32_t *object_ids, const double *corners) {
+  return edit_from_host(s, EDIT_QUADS, n, object_ids, corners);
+}
+int rt_scene_move_quads_device(rt_scene *s, int32_t n, const int32_t *device_object_ids,
+                               const double *device_corners, void *hip_stream) {
+  return edit_from_device(s, EDIT_QUADS, n, device_object_ids, device_corners, hip_stream);
 }
 
 // ---------------------------------------------------------------- rebuilding the world tree
@@ -1889,6 +1993,20 @@ int rt_multi_move_spheres(rt_multi *m, int32_t n, const int32_t *object_ids, con
   // the shards hold one description: what the first refuses none has applied
   for (rt_scene *s : m->scenes)
     if (int rc = rt_scene_move_spheres(s, n, object_ids, centres)) return rc;
+  return RT_OK;
+}
+
+int rt_multi_set_transforms(rt_multi *m, int32_t n, const int32_t *object_ids, const double *values) {
+  if (!m) return set_err(RT_ERR_INVALID, "null argument");
+  for (rt_scene *s : m->scenes) // one description: what the first refuses none has applied
+    if (int rc = rt_scene_set_transforms(s, n, object_ids, values)) return rc;
+  return RT_OK;
+}
+
+int rt_multi_move_quads(rt_multi *m, int32_t n, const int32_t *object_ids, const double *corners) {
+  if (!m) return set_err(RT_ERR_INVALID, "null argument");
+  for (rt_scene *s : m->scenes)
+    if (int rc = rt_scene_move_quads(s, n, object_ids, corners)) return rc;
   return RT_OK;
 }
 

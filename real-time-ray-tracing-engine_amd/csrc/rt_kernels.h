@@ -10,6 +10,7 @@
 
 #include "rt_layout.h"
 #include "rt_lds_plan.h"
+#include "rt_live.h"
 
 extern "C" {
 
@@ -151,6 +152,25 @@ struct RefitMove {
   int32_t n_roots, pad_;
 };
 hipError_t rtk_move_spheres(const RefitMove *m, hipStream_t st);
+// Live transforms and quads (rt_live.h: the entry rules and what an entry writes).  Entry j of
+// ids / values (n x 3 fp64) is applied when rt_live::transform_entry / quad_entry accepts it and
+// no other accepted entry names its object; any other entry is skipped.  index: device pointers;
+// named: n_objects counters (scratch).
+struct LiveEdit {
+  const int32_t *ids;
+  const double *values;
+  int32_t n, pad_;
+  rt_live::LiveIndex index;
+  unsigned *named;
+  DXform *xforms;
+  DQuad *quads;
+};
+hipError_t rtk_set_transforms(const LiveEdit *e, hipStream_t st);
+hipError_t rtk_move_quads(const LiveEdit *e, hipStream_t st);
+// each world medium's box from the tables (rt_refit.h medium_box) into mbox (6 floats per medium)
+hipError_t rtk_medium_boxes(const DItem *mitems, int n_mitems, const DMedium *media, const DItem *bitems,
+                            const DSphere *spheres, const DQuad *quads, const DXform *xforms, float *mbox,
+                            hipStream_t st);
 
 } // extern "C"
 #endif

@@ -5,11 +5,14 @@
 // The scene compiler (rt_scene.cpp) computes each item's fp64 world box from
 // the caller's description with the reference's rules (AABB.cpp:7-27, 167-175;
 // Sphere.cpp:15-23; Plane.cpp:17-20; RotateY.cpp:10-34; AABBUtility.hpp:7-11).
-// After spheres have moved (rt_scene_move_spheres) the description is gone, so
+// After spheres have moved (rt_scene_move_spheres) or transforms and quads have
+// been edited (rt_scene_set_transforms, rt_scene_move_quads; rt_live.h) the
+// description is gone, so
 // the same rules are restated here over DSphere / DQuad / DXform, operation by
 // operation: for a scene that has not moved, the boxes -- and so every refitted
 // node -- are the compiler's bit for bit (tests/test_refit.py holds them to
-// that over every committed scene).  Built with -ffp-contract=off like
+// that over every committed scene; tests/test_live_edits.py holds medium_box,
+// a world medium's fp32 box, to the compiler's mbox likewise).  Built with -ffp-contract=off like
 // rt_scene.cpp; nothing here may be contracted.
 //
 // The radius is sqrt(rr): DSphere keeps r*r and 1/r, and sqrt(r*r) == r for
@@ -132,6 +135,15 @@ RT_REFIT_HD Bx item_box(const DItem &it, const DSphere *spheres, const DQuad *qu
   return b;
 }
 
+RT_REFIT_HD Bx bx_empty() { // the compiler's empty box
+  Bx b;
+  for (int i = 0; i < 3; ++i) {
+    b.lo[i] = INFINITY;
+    b.hi[i] = -INFINITY;
+  }
+  return b;
+}
+
 // fp32 bounds rounded outward with the builders' margins (rt_scene.cpp
 // SahBuilder::f32_lo / f32_hi; nextafter written on the bits, as
 // rt_bvh_build.hip has it).
@@ -166,6 +178,27 @@ RT_REFIT_HD float f32_hi(double x) {
   float f = (float)m;
   if ((double)f < m) f = next_up(f);
   return f;
+}
+
+// The world box of a world medium item (DScene::mbox's six floats, lo xyz then
+// hi xyz): the join of its boundary items' boxes, each under its own chain in
+// the medium's local frame, then the medium item's chain, innermost first,
+// rounded outward -- the compiler's make_item and run() (rt_scene.cpp), operation
+// by operation.  Nothing here reads DMedium's face constants (bnk, bD, bB):
+// they are functions of the boundary quads in the boundary's frame alone.
+RT_REFIT_HD void medium_box(const DItem &m, const DMedium *media, const DItem *bitems, const DSphere *spheres,
+                            const DQuad *quads, const DXform *xforms, float out[6]) {
+  const DMedium &md = media[m.idx];
+  Bx b = bx_empty();
+  for (int k = 0; k < md.b_count; ++k) b = bx_join(b, item_box(bitems[md.b_first + k], spheres, quads, xforms));
+  for (int k = m.xf_count; k-- > 0;) {
+    const DXform &x = xforms[m.xf_first + k];
+    b = x.kind == X_ROTATE_Y ? rot_box(b, x.a, x.b) : trans_box(b, x.a, x.b, x.c);
+  }
+  for (int a = 0; a < 3; ++a) {
+    out[a] = f32_lo(b.lo[a]);
+    out[3 + a] = f32_hi(b.hi[a]);
+  }
 }
 
 // A node of either width as the refit sees it: DNode (A = 2) and DNode4

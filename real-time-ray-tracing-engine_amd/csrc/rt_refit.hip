@@ -21,12 +21,18 @@
 //                     refit_boxes: the 8 XCDs' L2s are not coherent, the
 //                     release / acquire pair is what makes a sibling's slot
 //                     visible to the last arrival.
+// Transforms and quads of a live scene are edited the same way (xform_count /
+// xform_apply, quad_count / quad_apply; rt_live.h holds the entry rules), and
+// every update, a sphere move included, is followed by medium_boxes: one thread
+// per world medium recomputes DScene::mbox from the medium's boundary items and
+// chain (rt_refit.h medium_box), before steps 2 and 3.
 // Every refit is a full one over boxes computed from the tables, so the tree
 // never depends on the history of moves; unions of fp32 boxes are exact, so
 // the result does not depend on the arrival order either.
 // The links (each node's parent slot and child count) are built once per scene
 // by refit_links, over any node order: linear BVHs are not in BFS order.
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "rt_kernels.h"
@@ -123,6 +129,54 @@ __global__ void move_apply(RefitMove m) {
       for (int a = 0; a < 3; ++a) m.roots[r].test.c0[a] = c[a];
 }
 
+// Live transforms and quads (rt_live.h): count, then apply, as the sphere move
+// does; an object named by two acceptable entries is written by neither.
+__global__ void xform_count(LiveEdit e) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= e.n) return;
+  if (rt_live::transform_entry(e.index, e.ids[j], e.values + 3 * (size_t)j) == rt_live::LIVE_OK)
+    atomicAdd(&e.named[e.ids[j]], 1u);
+}
+__global__ void xform_apply(LiveEdit e) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= e.n) return;
+  const double *v = e.values + 3 * (size_t)j;
+  if (rt_live::transform_entry(e.index, e.ids[j], v) != rt_live::LIVE_OK || e.named[e.ids[j]] != 1u) return;
+  rt_live::apply_transform(e.index, e.ids[j], v, e.xforms);
+}
+// DQuad::n read in place: record r's normal is normals_of(quads) + kQuadStride * r
+const int kQuadStride = sizeof(DQuad) / sizeof(double);
+static_assert(sizeof(DQuad) % sizeof(double) == 0 && offsetof(DQuad, n) % sizeof(double) == 0, "DQuad is a row of doubles");
+__device__ __forceinline__ const double *normals_of(const DQuad *quads) {
+  return reinterpret_cast<const double *>(quads) + offsetof(DQuad, n) / sizeof(double);
+}
+__global__ void quad_count(LiveEdit e) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= e.n) return;
+  double D;
+  if (rt_live::quad_entry(e.index, e.ids[j], e.values + 3 * (size_t)j, normals_of(e.quads), kQuadStride, D) == rt_live::LIVE_OK)
+    atomicAdd(&e.named[e.ids[j]], 1u);
+}
+__global__ void quad_apply(LiveEdit e) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= e.n) return;
+  const double *c = e.values + 3 * (size_t)j;
+  double D;
+  if (rt_live::quad_entry(e.index, e.ids[j], c, normals_of(e.quads), kQuadStride, D) != rt_live::LIVE_OK ||
+      e.named[e.ids[j]] != 1u)
+    return;
+  rt_live::apply_quad(e.quads[e.index.quad_of[e.ids[j]]], c, D);
+}
+
+__global__ void medium_boxes(const DItem *mitems, int n_mitems, const DMedium *media, const DItem *bitems,
+                             const DSphere *spheres, const DQuad *quads, const DXform *xforms, float *mbox) {
+  const int m = blockIdx.x * blockDim.x + threadIdx.x;
+  if (m >= n_mitems) return;
+  float six[6];
+  rt_refit::medium_box(mitems[m], media, bitems, spheres, quads, xforms, six);
+  for (int a = 0; a < 6; ++a) mbox[6 * (size_t)m + a] = six[a];
+}
+
 size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 
 struct Temp {
@@ -215,5 +269,32 @@ extern "C" hipError_t rtk_move_spheres(const RefitMove *m, hipStream_t st) {
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(move_count, dim3(grid(m->n)), dim3(B), 0, st, *m);
   hipLaunchKernelGGL(move_apply, dim3(grid(m->n)), dim3(B), 0, st, *m);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t rtk_set_transforms(const LiveEdit *e, hipStream_t st) {
+  if (e->n <= 0) return hipSuccess;
+  hipError_t err = hipMemsetAsync(e->named, 0, sizeof(unsigned) * (size_t)e->index.n_objects, st);
+  if (err != hipSuccess) return err;
+  hipLaunchKernelGGL(xform_count, dim3(grid(e->n)), dim3(B), 0, st, *e);
+  hipLaunchKernelGGL(xform_apply, dim3(grid(e->n)), dim3(B), 0, st, *e);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t rtk_move_quads(const LiveEdit *e, hipStream_t st) {
+  if (e->n <= 0) return hipSuccess;
+  hipError_t err = hipMemsetAsync(e->named, 0, sizeof(unsigned) * (size_t)e->index.n_objects, st);
+  if (err != hipSuccess) return err;
+  hipLaunchKernelGGL(quad_count, dim3(grid(e->n)), dim3(B), 0, st, *e);
+  hipLaunchKernelGGL(quad_apply, dim3(grid(e->n)), dim3(B), 0, st, *e);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t rtk_medium_boxes(const DItem *mitems, int n_mitems, const DMedium *media, const DItem *bitems,
+                                       const DSphere *spheres, const DQuad *quads, const DXform *xforms, float *mbox,
+                                       hipStream_t st) {
+  if (n_mitems <= 0) return hipSuccess;
+  hipLaunchKernelGGL(medium_boxes, dim3(grid(n_mitems)), dim3(B), 0, st, mitems, n_mitems, media, bitems, spheres,
+                     quads, xforms, mbox);
   return hipGetLastError();
 }

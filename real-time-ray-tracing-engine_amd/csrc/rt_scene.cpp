@@ -543,9 +543,7 @@ struct Compiler {
       c = x.a.y;
       return;
     }
-    double rad = x.s * kPi / 180.0;
-    s = std::sin(rad);
-    c = std::cos(rad);
+    rt_rotate_y_sincos(x.s, &s, &c);
   }
 
   int sphere_record(int o) {
@@ -609,6 +607,7 @@ struct Compiler {
   }
 
   std::map<std::vector<int>, int> chain_first; // identical chains share their xforms
+  std::vector<int32_t> xform_obj;              // the object each xforms[] record came from
   int emit_chain(const std::vector<int> &chain) {
     if (chain.empty()) return 0;
     auto known = chain_first.find(chain);
@@ -629,8 +628,28 @@ struct Compiler {
         rot_sincos(x, X.a, X.b);
       }
       H.xforms.push_back(X);
+      xform_obj.push_back(o);
     }
     return first;
+  }
+
+  // HostScene's live-edit index (rt_scene.h), once every record has been emitted.
+  void emit_live_index() {
+    const int n = D->n_objects;
+    H.xf_kind.assign(n, -1);
+    H.xf_first.assign(n + 1, 0);
+    for (int o = 0; o < n; ++o) {
+      if (D->objects[o].kind == RT_OBJ_TRANSLATE) H.xf_kind[o] = X_TRANSLATE;
+      if (D->objects[o].kind == RT_OBJ_ROTATE_Y) H.xf_kind[o] = X_ROTATE_Y;
+    }
+    for (int32_t o : xform_obj) ++H.xf_first[o + 1];
+    for (int o = 0; o < n; ++o) H.xf_first[o + 1] += H.xf_first[o];
+    H.xf_recs.assign(xform_obj.size(), 0);
+    std::vector<int32_t> next(H.xf_first.begin(), H.xf_first.end() - 1);
+    for (size_t r = 0; r < xform_obj.size(); ++r) H.xf_recs[next[xform_obj[r]]++] = (int32_t)r;
+    H.quad_of = quad_of; // quad_record: world items, light leaves and boundary items alike
+    for (const DItem &it : H.bitems)
+      if (it.kind == I_QUAD) H.quad_of[it.id] = -2;
   }
 
   // Reference box rules for RotateY (RotateY.cpp:10-34) and Translate
@@ -1018,7 +1037,9 @@ struct Compiler {
     } else {
       SahBuilder(H).emit_world_bvh(ibox);
     }
-    return emit_lights();
+    if (!emit_lights()) return false;
+    emit_live_index();
+    return true;
   }
 };
 
@@ -1239,3 +1260,14 @@ int launch_geometry(const rt_frame *f, const rt_render_params *p, DLaunch &L, st
 }
 
 } // namespace rtx
+
+// RotateY's (sin, cos) of an angle in degrees (RotateY.cpp:7-9), stated once:
+// the compiler's rot_sincos calls it, so a caller of rt_scene_set_transforms
+// gets the pair a scene created with that angle holds.
+extern "C" int rt_rotate_y_sincos(double degrees, double *sin_theta, double *cos_theta) {
+  if (!sin_theta || !cos_theta) return RT_ERR_INVALID;
+  const double rad = degrees * rtx::kPi / 180.0;
+  *sin_theta = std::sin(rad);
+  *cos_theta = std::cos(rad);
+  return RT_OK;
+}

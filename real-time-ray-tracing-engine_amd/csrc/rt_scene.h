@@ -44,6 +44,14 @@ struct HostScene {
   int32_t sah_leaf_max = 0, sah_leaf_split = 0, sah_trav_x4 = 0, sah_bins = 0;
   std::vector<double> item_boxes;
   double scene_lo[3] = {0, 0, 0}, scene_hi[3] = {0, 0, 0};
+  // Live edits (rt_scene_set_transforms*, rt_scene_move_quads*; rt_live.h LiveIndex), one entry
+  // per object of the description:
+  //   xf_kind      X_TRANSLATE / X_ROTATE_Y for a translate / rotate_y object, -1 for any other;
+  //   xf_first     CSR offsets (n_objects + 1) into xf_recs, the xforms[] records emit_chain wrote
+  //                for the object: one per distinct chain it stands in ([T] and [T, R] are two);
+  //   quad_of      a quad's DQuad record when it is a world primitive item or a light leaf, -1
+  //                when the object has no such record, -2 when it (also) bounds a medium.
+  std::vector<int32_t> xf_kind, xf_first, xf_recs, quad_of;
 };
 
 // 1 when no sphere moves (DScene::static_spheres): a flat world then runs the

@@ -259,4 +259,6 @@ EXPORTS = (
     "rt_guided_select_device",
     "rt_scene_move_spheres", "rt_scene_move_spheres_device", "rt_multi_move_spheres",
     "rt_scene_rebuild_bvh", "rt_multi_rebuild_bvh",
+    "rt_scene_set_transforms", "rt_scene_set_transforms_device", "rt_multi_set_transforms",
+    "rt_scene_move_quads", "rt_scene_move_quads_device", "rt_multi_move_quads", "rt_rotate_y_sincos",
 )

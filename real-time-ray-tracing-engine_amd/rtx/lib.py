@@ -100,6 +100,11 @@ def load():
     L.rt_multi_move_spheres.argtypes = [C.c_void_p, C.c_int32, P(C.c_int32), P(C.c_double)]
     L.rt_scene_rebuild_bvh.argtypes = [C.c_void_p, P(C.c_int32)]
     L.rt_multi_rebuild_bvh.argtypes = [C.c_void_p, P(C.c_int32)]
+    for edit in ("set_transforms", "move_quads"):
+        getattr(L, "rt_scene_" + edit).argtypes = [C.c_void_p, C.c_int32, P(C.c_int32), P(C.c_double)]
+        getattr(L, "rt_scene_" + edit + "_device").argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        getattr(L, "rt_multi_" + edit).argtypes = [C.c_void_p, C.c_int32, P(C.c_int32), P(C.c_double)]
+    L.rt_rotate_y_sincos.argtypes = [C.c_double, P(C.c_double), P(C.c_double)]
     for name in abi.EXPORTS:
         getattr(L, name).restype = C.c_char_p if name == "rt_last_error" else C.c_int
     if L.rt_abi_version() != abi.RT_ABI_VERSION:

@@ -34,6 +34,32 @@ def describe_move(scene, ids, centres):
         o.a = abi.Vec3.of([float(c[0]), float(c[1]), float(c[2])])
 
 
+def rotate_y_row(degrees):
+    """The set_transforms row of a rotate_y by `degrees`: (sin, cos, 0) exactly
+    as scene creation computes them (rt_rotate_y_sincos)."""
+    sn, cs = C.c_double(), C.c_double()
+    check(load().rt_rotate_y_sincos(float(degrees), C.byref(sn), C.byref(cs)))
+    return [sn.value, cs.value, 0.0]
+
+
+def describe_transforms(scene, ids, values):
+    """set_transforms in the SceneDescription: a translate gets its offset, a
+    rotate_y becomes the stored form (moving = RT_STORED_FORM, a = (sin, cos, 0))."""
+    for i, v in zip(ids, values):
+        o = scene.objects[int(i)]
+        if o.kind == abi.RT_OBJ_ROTATE_Y:
+            o.moving = abi.RT_STORED_FORM
+            o.a = abi.Vec3.of([float(v[0]), float(v[1]), 0.0])
+        else:
+            o.a = abi.Vec3.of([float(v[0]), float(v[1]), float(v[2])])
+
+
+def describe_quads(scene, ids, corners):
+    """move_quads in the SceneDescription: the corner Q."""
+    for i, c in zip(ids, corners):
+        scene.objects[int(i)].a = abi.Vec3.of([float(c[0]), float(c[1]), float(c[2])])
+
+
 def camera_frame(cam):
     """Camera::initialize (Camera.cpp:31-73) via rt_camera_setup."""
     f = abi.Frame()
@@ -198,6 +224,41 @@ class Renderer:
         check(self.lib.rt_scene_move_spheres_device(self.handle, int(n), C.c_void_p(ids_ptr),
                                                     C.c_void_p(centres_ptr), C.c_void_p(stream_ptr or 0)))
 
+    def _edit(self, fn, ids, values):
+        ids, values = _move_arrays(ids, values)
+        check(fn(self.handle, len(ids), ids.ctypes.data_as(C.POINTER(C.c_int32)),
+                 values.ctypes.data_as(C.POINTER(C.c_double))))
+        return ids, values
+
+    def set_transforms(self, ids, values):
+        """rt_scene_set_transforms: the translate / rotate_y objects `ids` get
+        `values` ([n, 3]: an offset, or (sin, cos, ignored) -- rotate_y_row
+        gives the row of an angle); every medium's world box and the world BVH
+        follow on the device.  Synchronous.  The SceneDescription follows as
+        with move_spheres, and as there whatever was accumulated or displayed
+        before describes the old scene: reset() it."""
+        describe_transforms(self.scene_desc, *self._edit(self.lib.rt_scene_set_transforms, ids, values))
+
+    def set_transforms_device(self, ids_ptr, values_ptr, n, stream_ptr=None):
+        """rt_scene_set_transforms_device: the same from device arrays (int32
+        [n], float64 [n, 3]) asynchronously on `stream_ptr`; an entry
+        set_transforms would refuse is skipped.  The SceneDescription is not
+        touched."""
+        check(self.lib.rt_scene_set_transforms_device(self.handle, int(n), C.c_void_p(ids_ptr),
+                                                      C.c_void_p(values_ptr), C.c_void_p(stream_ptr or 0)))
+
+    def move_quads(self, ids, corners):
+        """rt_scene_move_quads: the quads `ids` (world primitives or entries of
+        the lights list) get the corners Q `corners` ([n, 3]); u and v stay.
+        Synchronous; the SceneDescription follows."""
+        describe_quads(self.scene_desc, *self._edit(self.lib.rt_scene_move_quads, ids, corners))
+
+    def move_quads_device(self, ids_ptr, corners_ptr, n, stream_ptr=None):
+        """rt_scene_move_quads_device: the same from device arrays,
+        asynchronously on `stream_ptr`; the SceneDescription is not touched."""
+        check(self.lib.rt_scene_move_quads_device(self.handle, int(n), C.c_void_p(ids_ptr),
+                                                  C.c_void_p(corners_ptr), C.c_void_p(stream_ptr or 0)))
+
     def rebuild_bvh(self):
         """rt_scene_rebuild_bvh: a new world BVH over the spheres where they
         are now, built on the device -- the tree, info() and bvh_cost() of a
@@ -255,6 +316,16 @@ class MultiRenderer:
         check(self.lib.rt_multi_move_spheres(self.handle, len(ids), ids.ctypes.data_as(C.POINTER(C.c_int32)),
                                              centres.ctypes.data_as(C.POINTER(C.c_double))))
         describe_move(self.scene_desc, ids, centres)
+
+    _edit = Renderer._edit
+
+    def set_transforms(self, ids, values):
+        """rt_multi_set_transforms: Renderer.set_transforms on every shard's scene."""
+        describe_transforms(self.scene_desc, *self._edit(self.lib.rt_multi_set_transforms, ids, values))
+
+    def move_quads(self, ids, corners):
+        """rt_multi_move_quads: Renderer.move_quads on every shard's scene."""
+        describe_quads(self.scene_desc, *self._edit(self.lib.rt_multi_move_quads, ids, corners))
 
     def rebuild_bvh(self):
         """rt_multi_rebuild_bvh: Renderer.rebuild_bvh on every shard's scene;

@@ -35,6 +35,16 @@ a 4-wide tree) -- one JSON line each for
             rt_scene_bvh_cost of a 4-wide scene is creation's figure (rt_api.h):
             there only frame_ms shows the refitted tree's quality.
 
+With --instances N [N ...] the script runs the live-transform leg instead
+(log: profiles/set_transforms_bench.log): a world of N
+translate(rotate_y(box)) instances of one box on a grid (6 N world quads under
+2 N transform records), one JSON line each for
+
+  set_transforms  set_ms: one rt_scene_set_transforms_device of every translate
+            (the records, every item's box, full refit), the mean of `reps`
+            calls between HIP events; recreate_ms: rt_scene_destroy +
+            rt_scene_create of the same description, host clock, the best of 3.
+
 The lines go to stdout and to --log.  No test asserts any of these numbers."""
 import argparse
 import ctypes as C
@@ -78,6 +88,70 @@ def random_world(n, seed=1):
     return S
 
 
+def instance_world(n, seed=2):
+    """n instances translate(rotate_y(box)) of one 6 x 9 x 6 box on a square grid of pitch 12, over a floor quad."""
+    from rtx import abi
+    from rtx.scene import SceneDescription, make_box_quads
+    rng = np.random.default_rng(seed)
+    side = int(np.ceil(np.sqrt(n)))
+    S = SceneDescription()
+    half = 6.0 * side
+    S.camera = {"aspect_ratio": 1.0, "vfov": 50.0, "lookfrom": [0, 0.9 * half, 2.2 * half], "lookat": [0, 0, 0],
+                "background": [0.7, 0.8, 1.0]}
+    mat = S.add_material(abi.RT_MAT_LAMBERTIAN, texture=S.add_texture(abi.RT_TEX_SOLID, color=(0.6, 0.6, 0.6)))
+    box = S.add_list([S.add_object(abi.RT_OBJ_QUAD, material=mat, a=q, b=u, c=v)
+                      for q, u, v in make_box_quads([0, 0, 0], [6, 9, 6])])
+    angles = rng.uniform(-45, 45, size=n)
+    ids, translates = [], []
+    for k in range(n):
+        rot = S.add_object(abi.RT_OBJ_ROTATE_Y, child=box, s=float(angles[k]))
+        offset = (12.0 * (k % side) - half, 0.0, 12.0 * (k // side) - half)
+        translates.append(S.add_object(abi.RT_OBJ_TRANSLATE, child=rot, a=offset))
+    ids = translates + [S.add_object(abi.RT_OBJ_QUAD, material=mat, a=(-2 * half, 0, -2 * half), b=(4 * half, 0, 0),
+                                     c=(0, 0, 4 * half))]
+    S.world = S.add_list(ids)
+    return S, np.array(translates, dtype=np.int32)
+
+
+def set_transforms_leg(args):
+    """One line per instance count: every translate set on the device against destroy + create."""
+    import torch
+    from rtx.lib import check
+    from rtx.render import Renderer
+    for n in args.instances:
+        S, ids = instance_world(n)
+        offsets = np.array([[S.objects[i].a.x, S.objects[i].a.y, S.objects[i].a.z] for i in ids])
+        stream = torch.cuda.current_stream()
+        t = time.perf_counter()
+        R = Renderer(S)
+        create_ms = [(time.perf_counter() - t) * 1e3]
+        info = R.info()
+        for _ in range(3):  # destroy + create through the ABI alone, as the sphere leg does
+            h = C.c_void_p()
+            t = time.perf_counter()
+            check(R.lib.rt_scene_destroy(R.handle))
+            check(R.lib.rt_scene_create(C.byref(R._desc), 0, C.byref(h)))
+            create_ms.append((time.perf_counter() - t) * 1e3)
+            R.handle = h
+        d_ids = torch.from_numpy(ids).cuda()
+        d_new = torch.from_numpy(offsets + np.array([0.25, 0.0, -0.25])).cuda()  # the work does not depend on the values
+        edit = lambda: R.set_transforms_device(d_ids.data_ptr(), d_new.data_ptr(), len(ids), stream.cuda_stream)  # noqa: E731
+        for _ in range(3):
+            edit()
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        t0.record(stream)
+        for _ in range(args.reps):
+            edit()
+        t1.record(stream)
+        t1.synchronize()
+        say(kind="set_transforms", instances=n, world_items=info["n_leaf_refs"], transforms_set=len(ids),
+            builder=info["bvh_builder"], arity=info["bvh_arity"], nodes=info["n_nodes"],
+            set_ms=t0.elapsed_time(t1) / args.reps, recreate_ms=min(create_ms[1:]),
+            first_create_with_python_ms=create_ms[0])
+        R.close()
+
+
 def world(n):
     from rtx.scene import load_scene
     if n == 486:
@@ -113,14 +187,22 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--sizes", type=int, nargs="+", default=[486, 100000, 1000000])
     ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--log", default=os.path.join(ROOT, "profiles", "rebuild_bench.log"))
+    ap.add_argument("--instances", type=int, nargs="+", default=None,
+                    help="run the live-transform leg on worlds of this many box instances (e.g. 400 100000)")
+    ap.add_argument("--log", default=None)
     args = ap.parse_args()
+    if args.log is None:
+        args.log = os.path.join(ROOT, "profiles", "set_transforms_bench.log" if args.instances else "rebuild_bench.log")
     import torch
     from rtx import abi
     from rtx.lib import check
     from rtx.render import Renderer, camera_frame, describe_move
     os.makedirs(os.path.dirname(os.path.abspath(args.log)), exist_ok=True)
     LOG = open(args.log, "a")
+    if args.instances:
+        set_transforms_leg(args)
+        LOG.close()
+        return
     for n in args.sizes:
         S, step = world(n)
         cam = S.camera_desc(image_width=1920, aspect_ratio=16.0 / 9.0, samples_per_pixel=64, max_depth=8)
