@@ -1069,6 +1069,82 @@ int rt_multi_move_quads(rt_multi *multi, int32_t n, const int32_t *object_ids, c
    pointer. */
 int rt_rotate_y_sincos(double degrees, double *sin_theta, double *cos_theta);
 
+/* ---- ray queries (functions and two structs added under ABI 5: no struct or
+   signature above changed) ---------------------------------------------------
+   The edit calls above address objects by object_ids; these calls go the
+   other way: which object lies along a ray, in the same vocabulary (csrc/
+   rt_query.h, rt_query.hip; DESIGN.md "Ray queries").
+
+   The surface found is the render's closest primitive hit of
+   Ray{origin, direction, time} over the world's primitive items, in the
+   render's range (0.001, inf) in units of `direction` (Camera.cpp:242), with
+   the render's own search (rt_path.h trace_closest) and hit record
+   (trace_tail): the same tie rules, the same transform chains, moving spheres
+   at `time`.  `direction` need not be a unit vector; t counts in its length.
+
+   Constant media are not reported: a query has no RNG key, so a ray passes
+   through fog to the surface behind it (the scene's instance with
+   RT_FEAT_MEDIA and RT_FEAT_LIGHTS masked).
+
+   t_max: a hit counts when t <= t_max.  +inf, and every t_max <= 0 (-inf
+   included), mean no limit; a NaN t_max makes the ray a miss.  The search is
+   the unlimited one and its minimum is compared with t_max afterwards.
+
+   A ray with a zero direction, or with a NaN or infinite origin, direction or
+   time component, is a miss, decided before anything is walked.
+
+   The result of a ray does not depend on the rays around it, on its position
+   in the array, or on the tree (host-built, device-built, refitted, rebuilt,
+   binary or 4-wide): it gives the same bytes in every case. */
+typedef struct rt_ray {
+  double origin[3];
+  double direction[3];
+  double time;
+  double t_max;
+} rt_ray; /* 64 B */
+
+typedef struct rt_ray_hit {
+  double t;     /* in units of `direction`; +inf for a miss */
+  double p[3];  /* origin + t direction, through the item's transform chain */
+  double n[3];  /* unit normal against the ray */
+  int32_t object;       /* index into rt_scene_desc.objects of the sphere or quad hit:
+                           what rt_scene_move_spheres / rt_scene_move_quads take */
+  int32_t chain_object; /* the outermost translate or rotate_y above it (the first
+                           entry of its chain): what rt_scene_set_transforms takes,
+                           and rt_object_desc.child leads from it down to `object`;
+                           -1 when the primitive stands under no transform */
+  int32_t material;     /* index into rt_scene_desc.materials */
+  int32_t front;        /* 1: the ray met the outside of the surface */
+} rt_ray_hit; /* 72 B; a miss: t = +inf, p = n = 0, object = chain_object =
+                 material = -1, front = 0 */
+
+/* device_hits[k] = the hit of device_rays[k] for k in [0, n): every record is
+   written exactly once with plain stores, nothing else is written.  Both
+   arrays are device memory of the scene's device, 8-byte aligned.
+   Asynchronous on hip_stream (NULL = the HIP null stream); a link of the
+   scene's launch chain like rt_render_guides_device: it sees every edit queued
+   before it, and rt_scene_destroy waits for it.  Uses none of the scene's
+   scratch and allocates nothing.  n = 0 queues nothing and returns RT_OK.
+   RT_ERR_INVALID, before anything is queued: a null scene, n < 0, a null
+   array with n > 0, n above 2^36. */
+int rt_trace_device(rt_scene *scene, int64_t n, const rt_ray *device_rays, rt_ray_hit *device_hits,
+                    void *hip_stream);
+
+/* The same with host arrays: staged through device memory on the scene's own
+   stream; the hits are in `hits` on return. */
+int rt_trace(rt_scene *scene, int64_t n, const rt_ray *rays, rt_ray_hit *hits);
+
+/* rt_trace on shard 0's scene (the shards hold one description). */
+int rt_multi_trace(rt_multi *multi, int64_t n, const rt_ray *rays, rt_ray_hit *hits);
+
+/* The ray through the point (x, y) of the frame's pixel grid, the one
+   rt_temporal_device reprojects along: (i, j) is the centre of pixel (i, j),
+     origin = center,
+     direction = pixel00_loc + x pixel_delta_u + y pixel_delta_v - center
+   (added left to right), time = 0, t_max = +inf.  No jitter and no defocus.
+   Host only: needs no scene and no device.  RT_ERR_INVALID: a null pointer. */
+int rt_pixel_ray(const rt_frame *frame, double x, double y, rt_ray *ray);
+
 /* ---- guided sampling (one function added under ABI 5: no struct or signature
    above changed) ------------------------------------------------------------
    rt_adaptive_select_device retires a tile by the new pose's own batch

@@ -123,6 +123,13 @@ struct rt_scene {
   } rb;
   char *rebuild = nullptr;
   char *own_nodes = nullptr;
+  // Ray queries (rt_trace*).  `xf_obj`: per xforms[] record the object it came
+  // from (rtx::xform_objects), uploaded at creation -- its own allocation, so
+  // the block and the DScene are what they were; `trace_buf` stages the host
+  // variant's rays and hits.
+  int32_t *xf_obj = nullptr;
+  char *trace_buf = nullptr;
+  size_t trace_bytes = 0;
 };
 
 namespace {
@@ -610,6 +617,16 @@ static void keep_movable(rt_scene *s, const rt_scene_desc *desc, rtx::HostScene 
   s->compile_items = std::move(H.compile_items.empty() ? H.items : H.compile_items);
 }
 
+// The ray queries' table (rt_scene::xf_obj), from the live index keep_movable kept.
+static int upload_xform_objects(rt_scene *s) {
+  const std::vector<int32_t> obj = rtx::xform_objects(s->xf_first, s->xf_recs);
+  hipError_t e = scene_alloc(s, (void **)&s->xf_obj, sizeof(int32_t) * obj.size());
+  if (e != hipSuccess)
+    return set_err(RT_ERR_OOM, std::string("hipMallocFromPoolAsync transform objects: ") + hipGetErrorString(e));
+  if (!obj.empty()) e = upload(s, s->xf_obj, obj.data(), sizeof(int32_t) * obj.size(), hipMemcpyHostToDevice);
+  return e == hipSuccess ? RT_OK : hip_err(e, "upload transform objects");
+}
+
 // The part of rt_scene_info a rebuild changes: the tree's size and depth, who
 // built it, and the residency plan that follows from them.
 static void fill_tree_info(rt_scene *s, const RtkLdsPlan &plan, int builder) {
@@ -667,6 +684,7 @@ int rt_scene_create_tuned(const rt_scene_desc *desc, int32_t device, const rt_tu
   if (rc == RT_OK) rc = collapse_world_tree(s.get(), H, want4);
   if (rc != RT_OK) return rc;
   keep_movable(s.get(), desc, H);
+  if ((rc = upload_xform_objects(s.get())) != RT_OK) return rc;
   Residency res;
   if ((rc = plan_residency(s.get(), s->ds.n_nodes, s->bvh_depth, s->bvh_depth4, res)) != RT_OK) return rc;
   commit_residency(s.get(), res, plan);
@@ -699,6 +717,8 @@ int rt_scene_destroy(rt_scene *s) {
   bury(s, s->move_buf);
   bury(s, s->rebuild);
   bury(s, s->own_nodes);
+  bury(s, s->xf_obj);
+  bury(s, s->trace_buf);
   for (auto &o : s->order) bury(s, o.tile_cost); // the slot's one allocation
   bury(s, s->block);
   if (s->last) (void)hipEventDestroy(s->last);
@@ -1084,6 +1104,69 @@ int rt_render_guides_device(rt_scene *s, const rt_frame *f, const rt_render_para
   hipError_t e = rtk_launch_guides(&s->ds, &C, &L, dev_guides, st);
   if (e != hipSuccess) return hip_err(e, "guide kernel launch");
   return mark_last(s, st);
+}
+
+// ---------------------------------------------------------------- ray queries
+// One launch of the query kernel (rt_query.hip) on `st`: a link of the scene's
+// chain like the guide launch -- it reads the tables the edits write, so it
+// runs after whatever was queued before it, and destroy waits for it.
+static int trace_check(const rt_scene *s, int64_t n, const void *rays, const void *hits) {
+  if (n < 0) return set_err(RT_ERR_INVALID, "negative ray count");
+  if (n > ((int64_t)1 << 36)) return set_err(RT_ERR_INVALID, "more than 2^36 rays in one call");
+  if (n > 0 && (!rays || !hits)) return set_err(RT_ERR_INVALID, "null ray or hit array");
+  if (!s) return set_err(RT_ERR_INVALID, "null scene");
+  return RT_OK;
+}
+static int trace_on_stream(rt_scene *s, int64_t n, const rt_ray *d_rays, rt_ray_hit *d_hits, hipStream_t st) {
+  int rc = order_after_last(s, st);
+  if (rc) return rc;
+  hipError_t e = rtk_launch_trace(&s->ds, s->xf_obj, n, d_rays, d_hits, st);
+  if (e != hipSuccess) return hip_err(e, "query kernel launch");
+  return mark_last(s, st);
+}
+
+int rt_trace_device(rt_scene *s, int64_t n, const rt_ray *device_rays, rt_ray_hit *device_hits, void *hip_stream) {
+  int rc = trace_check(s, n, device_rays, device_hits);
+  if (rc || n == 0) return rc;
+  DeviceGuard g(s->device);
+  return trace_on_stream(s, n, device_rays, device_hits, (hipStream_t)hip_stream);
+}
+
+int rt_trace(rt_scene *s, int64_t n, const rt_ray *rays, rt_ray_hit *hits) {
+  int rc = trace_check(s, n, rays, hits);
+  if (rc || n == 0) return rc;
+  DeviceGuard g(s->device);
+  const size_t ray_bytes = sizeof(rt_ray) * (size_t)n, hit_bytes = sizeof(rt_ray_hit) * (size_t)n;
+  // only this function uses trace_buf, on the scene's stream, and synchronises before it returns
+  if ((rc = grow(s, s->trace_buf, s->trace_bytes, align256(ray_bytes) + hit_bytes, Idle::Already,
+                 "hipMallocFromPoolAsync query")))
+    return rc;
+  const rt_ray *d_rays = (const rt_ray *)s->trace_buf;
+  rt_ray_hit *d_hits = (rt_ray_hit *)(s->trace_buf + align256(ray_bytes));
+  hipError_t e = hipMemcpyAsync(s->trace_buf, rays, ray_bytes, hipMemcpyHostToDevice, s->stream);
+  if (e == hipSuccess) {
+    rc = trace_on_stream(s, n, d_rays, d_hits, s->stream);
+    if (rc == RT_OK) e = hipMemcpyAsync(hits, d_hits, hit_bytes, hipMemcpyDeviceToHost, s->stream);
+  }
+  const hipError_t es = hipStreamSynchronize(s->stream);
+  if (rc) return rc;
+  if (e != hipSuccess) return hip_err(e, "query copy");
+  return es == hipSuccess ? RT_OK : hip_err(es, "query kernel");
+}
+
+int rt_pixel_ray(const rt_frame *f, double x, double y, rt_ray *ray) {
+  if (!f || !ray) return set_err(RT_ERR_INVALID, "null argument");
+  const double c[3] = {f->center.x, f->center.y, f->center.z};
+  const double p00[3] = {f->pixel00_loc.x, f->pixel00_loc.y, f->pixel00_loc.z};
+  const double du[3] = {f->pixel_delta_u.x, f->pixel_delta_u.y, f->pixel_delta_u.z};
+  const double dv[3] = {f->pixel_delta_v.x, f->pixel_delta_v.y, f->pixel_delta_v.z};
+  for (int a = 0; a < 3; ++a) { // rt_temporal.h centre_point's ray, at any (x, y)
+    ray->origin[a] = c[a];
+    ray->direction[a] = p00[a] + x * du[a] + y * dv[a] - c[a];
+  }
+  ray->time = 0.0;
+  ray->t_max = HUGE_VAL;
+  return RT_OK;
 }
 
 // a byte range of device memory; a null pointer spans nothing
@@ -2022,6 +2105,11 @@ int rt_multi_rebuild_bvh(rt_multi *m, int32_t *rebuilt) {
   }
   if (rebuilt) *rebuilt = m->scenes.empty() ? 0 : all;
   return RT_OK;
+}
+
+int rt_multi_trace(rt_multi *m, int64_t n, const rt_ray *rays, rt_ray_hit *hits) {
+  // the shards hold one description; a null multi is refused as rt_trace refuses a null scene
+  return rt_trace(m && !m->scenes.empty() ? m->scenes[0] : nullptr, n, rays, hits);
 }
 
 int rt_multi_shard_ms(rt_multi *m, double *ms) {

@@ -54,6 +54,17 @@ struct HostScene {
   std::vector<int32_t> xf_kind, xf_first, xf_recs, quad_of;
 };
 
+// The object each xforms[] record came from, one entry per record: the live
+// index above read the other way (ray queries, rt_query.h: the first record of
+// an item's chain names the outermost transform above it).  Its own table
+// beside the scene's: DScene and the bytes of its tables stay what they were.
+inline std::vector<int32_t> xform_objects(const std::vector<int32_t> &xf_first, const std::vector<int32_t> &xf_recs) {
+  std::vector<int32_t> obj(xf_recs.size(), -1);
+  for (size_t o = 0; o + 1 < xf_first.size(); ++o)
+    for (int32_t k = xf_first[o]; k < xf_first[o + 1]; ++k) obj[xf_recs[k]] = (int32_t)o;
+  return obj;
+}
+
 // 1 when no sphere moves (DScene::static_spheres): a flat world then runs the
 // static instantiation of its item walk and hit record (rt_path.h trace,
 // trace_tail), without the center.at(time) arithmetic, whose result is c0

@@ -230,6 +230,20 @@ def temporal_params(p=None):
 RT_GUIDED_FLOOR, RT_GUIDED_MIN_COUNT = 1e-2, 8
 
 
+class Ray(C.Structure):
+    """rt_ray (64 B): t_max <= 0 or +inf: no limit; NaN: a miss."""
+    _fields_ = [("origin", C.c_double * 3), ("direction", C.c_double * 3),
+                ("time", C.c_double), ("t_max", C.c_double)]
+
+
+class RayHit(C.Structure):
+    """rt_ray_hit (72 B).  A miss: t = +inf, p = n = 0, object = chain_object =
+    material = -1, front = 0."""
+    _fields_ = [("t", C.c_double), ("p", C.c_double * 3), ("n", C.c_double * 3),
+                ("object", C.c_int32), ("chain_object", C.c_int32),
+                ("material", C.c_int32), ("front", C.c_int32)]
+
+
 def tuning(t=None):
     """A Tuning from None (the default), a Tuning, or a dict of its fields."""
     if t is None or isinstance(t, Tuning):
@@ -261,4 +275,5 @@ EXPORTS = (
     "rt_scene_rebuild_bvh", "rt_multi_rebuild_bvh",
     "rt_scene_set_transforms", "rt_scene_set_transforms_device", "rt_multi_set_transforms",
     "rt_scene_move_quads", "rt_scene_move_quads_device", "rt_multi_move_quads", "rt_rotate_y_sincos",
+    "rt_trace_device", "rt_trace", "rt_multi_trace", "rt_pixel_ray",
 )

@@ -60,6 +60,40 @@ def describe_quads(scene, ids, corners):
         scene.objects[int(i)].a = abi.Vec3.of([float(c[0]), float(c[1]), float(c[2])])
 
 
+# rt_ray / rt_ray_hit as NumPy records (the layouts of abi.Ray / abi.RayHit)
+RAY_DTYPE = np.dtype([("origin", "<f8", 3), ("direction", "<f8", 3), ("time", "<f8"), ("t_max", "<f8")])
+HIT_DTYPE = np.dtype([("t", "<f8"), ("p", "<f8", 3), ("n", "<f8", 3), ("object", "<i4"),
+                      ("chain_object", "<i4"), ("material", "<i4"), ("front", "<i4")])
+
+
+def ray_array(rays):
+    """Rays as a contiguous RAY_DTYPE array [n]: from one, or from an [n, 8]
+    float64 array of rows (origin xyz, direction xyz, time, t_max)."""
+    a = np.asarray(rays)
+    if a.dtype == RAY_DTYPE:
+        return np.ascontiguousarray(a).reshape(-1)
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if a.ndim != 2 or a.shape[1] != 8:
+        raise ValueError("rays: an [n, 8] float64 array or a RAY_DTYPE array, not shape %r" % (a.shape,))
+    return a.view(RAY_DTYPE).reshape(-1)
+
+
+def pixel_ray(frame, x, y):
+    """rt_pixel_ray: the ray through the point (x, y) of the frame's pixel grid
+    ((i, j): the centre of pixel (i, j)); no jitter, no defocus, time 0, no
+    t_max.  A RAY_DTYPE array [1]."""
+    r = abi.Ray()
+    check(load().rt_pixel_ray(C.byref(frame), float(x), float(y), C.byref(r)))
+    return np.frombuffer(bytes(r), dtype=RAY_DTYPE).copy()
+
+
+def _trace(fn, handle, rays):
+    rays = ray_array(rays)
+    hits = np.empty(len(rays), dtype=HIT_DTYPE)
+    check(fn(handle, len(rays), C.c_void_p(rays.ctypes.data), C.c_void_p(hits.ctypes.data)))
+    return hits
+
+
 def camera_frame(cam):
     """Camera::initialize (Camera.cpp:31-73) via rt_camera_setup."""
     f = abi.Frame()
@@ -269,6 +303,27 @@ class Renderer:
         check(self.lib.rt_scene_rebuild_bvh(self.handle, C.byref(took)))
         return bool(took.value)
 
+    def trace(self, rays):
+        """rt_trace: the closest surface along each ray ([n, 8] float64 rows of
+        origin, direction, time, t_max, or a RAY_DTYPE array) as a HIT_DTYPE
+        array [n]: t, p, n, and the hit's `object` (what move_spheres /
+        move_quads take), `chain_object` (what set_transforms takes; -1: none),
+        `material` and `front`.  Constant media are passed through; a miss has
+        object -1 and t = inf.  Synchronous."""
+        return _trace(self.lib.rt_trace, self.handle, rays)
+
+    def trace_device(self, rays_ptr, hits_ptr, n, stream_ptr=None):
+        """rt_trace_device: the same from a device array of n rt_ray into a
+        device array of n rt_ray_hit, asynchronously on `stream_ptr`, after
+        every edit queued before it."""
+        check(self.lib.rt_trace_device(self.handle, int(n), C.c_void_p(rays_ptr), C.c_void_p(hits_ptr),
+                                       C.c_void_p(stream_ptr or 0)))
+
+    def pick(self, frame, x, y):
+        """What lies under the point (x, y) of the frame: the hit of
+        pixel_ray(frame, x, y), one HIT_DTYPE record."""
+        return self.trace(pixel_ray(frame, x, y))[0]
+
 
 class MultiRenderer:
     """rt_multi_*: one device scene per shard (shard k on devices[k % len]),
@@ -326,6 +381,10 @@ class MultiRenderer:
     def move_quads(self, ids, corners):
         """rt_multi_move_quads: Renderer.move_quads on every shard's scene."""
         describe_quads(self.scene_desc, *self._edit(self.lib.rt_multi_move_quads, ids, corners))
+
+    def trace(self, rays):
+        """rt_multi_trace: Renderer.trace on shard 0's scene."""
+        return _trace(self.lib.rt_multi_trace, self.handle, rays)
 
     def rebuild_bvh(self):
         """rt_multi_rebuild_bvh: Renderer.rebuild_bvh on every shard's scene;
