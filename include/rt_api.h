@@ -1145,6 +1145,61 @@ int rt_multi_trace(rt_multi *multi, int64_t n, const rt_ray *rays, rt_ray_hit *h
    Host only: needs no scene and no device.  RT_ERR_INVALID: a null pointer. */
 int rt_pixel_ray(const rt_frame *frame, double x, double y, rt_ray *ray);
 
+/* ---- occlusion queries (four functions added under ABI 5: no struct or
+   signature above changed) ---------------------------------------------------
+   Line of sight, shadow and ambient-occlusion tests want a verdict, not a
+   record: is anything in the way (csrc/rt_occlusion.h, rt_occlusion.hip;
+   DESIGN.md "Occlusion queries").
+
+   occluded[k] is 1 exactly where rt_trace's record of the same rt_ray is a
+   hit, and 0 where it is a miss -- for every ray, not within a tolerance: the
+   same hit tests, transform chains, moving spheres at `time`, the same range
+   (0.001, t_max] in units of `direction`, constant media passed through, and
+   the same rules for t_max (+inf and every t_max <= 0: no limit; NaN:
+   unoccluded) and for bad rays (a zero direction, or a NaN or infinite origin,
+   direction or time component: unoccluded, decided from the bits before
+   anything is walked).
+
+   What differs is the search.  It is an any-hit walk of its own: the interval
+   is (0.001, t_max] from the first node on, so a short segment culls every box
+   beyond its end, and a ray stops at the first primitive it accepts, whichever
+   that is.  The verdict is still a property of the ray and the tables alone:
+   it does not depend on the tree (host-built, device-built, refitted, rebuilt,
+   binary, 4-wide or flat), on which blocker was met first, on the rays around
+   it or on its position in the array.
+
+   Not offered: transmittance through media, a caller t_min, a bit-mask
+   output. */
+
+/* device_occluded[k] = the verdict of device_rays[k] for k in [0, n): one
+   byte, 0 or 1, each written exactly once with a plain store; nothing else is
+   written.  Both arrays are device memory of the scene's device; the rays are
+   8-byte aligned, the bytes need no alignment (a bool buffer does).
+   Asynchronous on hip_stream (NULL = the HIP null stream); a link of the
+   scene's launch chain like rt_trace_device: it sees every edit queued before
+   it, and rt_scene_destroy waits for it.  Uses none of the scene's scratch
+   and allocates nothing.  n = 0 queues nothing and returns RT_OK.
+   RT_ERR_INVALID, before anything is queued: a null scene, n < 0, a null
+   array with n > 0, n above 2^36. */
+int rt_occluded_device(rt_scene *scene, int64_t n, const rt_ray *device_rays, uint8_t *device_occluded,
+                       void *hip_stream);
+
+/* The same with host arrays: staged through device memory on the scene's own
+   stream; the verdicts are in `occluded` on return. */
+int rt_occluded(rt_scene *scene, int64_t n, const rt_ray *rays, uint8_t *occluded);
+
+/* rt_occluded on shard 0's scene (the shards hold one description). */
+int rt_multi_occluded(rt_multi *multi, int64_t n, const rt_ray *rays, uint8_t *occluded);
+
+/* The ray that asks whether b is visible from a:
+     origin = a, direction = b - a (componentwise), time as given, t_max = 0.999.
+   The search starts at 0.001 in units of `direction`, which skips the surface
+   a stands on; 0.999 skips the surface b stands on by the same amount.  a == b
+   gives a zero direction and non-finite inputs go through unchanged: both are
+   unoccluded by the rule above.  Host only: needs no scene and no device.
+   RT_ERR_INVALID: a null pointer. */
+int rt_segment_ray(const double a[3], const double b[3], double time, rt_ray *ray);
+
 /* ---- guided sampling (one function added under ABI 5: no struct or signature
    above changed) ------------------------------------------------------------
    rt_adaptive_select_device retires a tile by the new pose's own batch

@@ -1137,7 +1137,7 @@ int rt_trace(rt_scene *s, int64_t n, const rt_ray *rays, rt_ray_hit *hits) {
   if (rc || n == 0) return rc;
   DeviceGuard g(s->device);
   const size_t ray_bytes = sizeof(rt_ray) * (size_t)n, hit_bytes = sizeof(rt_ray_hit) * (size_t)n;
-  // only this function uses trace_buf, on the scene's stream, and synchronises before it returns
+  // only this function and rt_occluded use trace_buf, on the scene's stream, and each synchronises before it returns
   if ((rc = grow(s, s->trace_buf, s->trace_bytes, align256(ray_bytes) + hit_bytes, Idle::Already,
                  "hipMallocFromPoolAsync query")))
     return rc;
@@ -1166,6 +1166,59 @@ int rt_pixel_ray(const rt_frame *f, double x, double y, rt_ray *ray) {
   }
   ray->time = 0.0;
   ray->t_max = HUGE_VAL;
+  return RT_OK;
+}
+
+// ---------------------------------------------------------- occlusion queries
+// One launch of the occlusion kernel (rt_occlusion.hip) on `st`: a link of the
+// scene's chain exactly as trace_on_stream is.
+static int occluded_on_stream(rt_scene *s, int64_t n, const rt_ray *d_rays, uint8_t *d_occ, hipStream_t st) {
+  int rc = order_after_last(s, st);
+  if (rc) return rc;
+  hipError_t e = rtk_launch_occluded(&s->ds, n, d_rays, d_occ, st);
+  if (e != hipSuccess) return hip_err(e, "occlusion kernel launch");
+  return mark_last(s, st);
+}
+
+int rt_occluded_device(rt_scene *s, int64_t n, const rt_ray *device_rays, uint8_t *device_occluded,
+                       void *hip_stream) {
+  int rc = trace_check(s, n, device_rays, device_occluded);
+  if (rc || n == 0) return rc;
+  DeviceGuard g(s->device);
+  return occluded_on_stream(s, n, device_rays, device_occluded, (hipStream_t)hip_stream);
+}
+
+int rt_occluded(rt_scene *s, int64_t n, const rt_ray *rays, uint8_t *occluded) {
+  int rc = trace_check(s, n, rays, occluded);
+  if (rc || n == 0) return rc;
+  DeviceGuard g(s->device);
+  const size_t ray_bytes = sizeof(rt_ray) * (size_t)n, occ_bytes = (size_t)n;
+  // trace_buf is rt_trace's and this function's: both use it on the scene's
+  // stream and synchronise before they return
+  if ((rc = grow(s, s->trace_buf, s->trace_bytes, align256(ray_bytes) + occ_bytes, Idle::Already,
+                 "hipMallocFromPoolAsync occlusion query")))
+    return rc;
+  const rt_ray *d_rays = (const rt_ray *)s->trace_buf;
+  uint8_t *d_occ = (uint8_t *)(s->trace_buf + align256(ray_bytes));
+  hipError_t e = hipMemcpyAsync(s->trace_buf, rays, ray_bytes, hipMemcpyHostToDevice, s->stream);
+  if (e == hipSuccess) {
+    rc = occluded_on_stream(s, n, d_rays, d_occ, s->stream);
+    if (rc == RT_OK) e = hipMemcpyAsync(occluded, d_occ, occ_bytes, hipMemcpyDeviceToHost, s->stream);
+  }
+  const hipError_t es = hipStreamSynchronize(s->stream);
+  if (rc) return rc;
+  if (e != hipSuccess) return hip_err(e, "occlusion query copy");
+  return es == hipSuccess ? RT_OK : hip_err(es, "occlusion kernel");
+}
+
+int rt_segment_ray(const double a[3], const double b[3], double time, rt_ray *ray) {
+  if (!a || !b || !ray) return set_err(RT_ERR_INVALID, "null argument");
+  for (int k = 0; k < 3; ++k) {
+    ray->origin[k] = a[k];
+    ray->direction[k] = b[k] - a[k];
+  }
+  ray->time = time;
+  ray->t_max = 0.999; // the search starts at 0.001: both ends' own surfaces are skipped alike
   return RT_OK;
 }
 
@@ -2110,6 +2163,10 @@ int rt_multi_rebuild_bvh(rt_multi *m, int32_t *rebuilt) {
 int rt_multi_trace(rt_multi *m, int64_t n, const rt_ray *rays, rt_ray_hit *hits) {
   // the shards hold one description; a null multi is refused as rt_trace refuses a null scene
   return rt_trace(m && !m->scenes.empty() ? m->scenes[0] : nullptr, n, rays, hits);
+}
+
+int rt_multi_occluded(rt_multi *m, int64_t n, const rt_ray *rays, uint8_t *occluded) {
+  return rt_occluded(m && !m->scenes.empty() ? m->scenes[0] : nullptr, n, rays, occluded); // as rt_multi_trace
 }
 
 int rt_multi_shard_ms(rt_multi *m, double *ms) {

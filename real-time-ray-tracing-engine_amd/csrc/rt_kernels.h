@@ -1,6 +1,6 @@
 // rt_kernels.h — every rtk_* launcher, declared once: included by the files
 // that define them (rt_kernel.hip, rt_frame.hip, rt_adaptive.hip, rt_guides.hip,
-// rt_denoise.hip, rt_temporal.hip, rt_bvh_build.hip, rt_bvh_sah.hip, rt_collapse.hip, rt_refit.hip, rt_query.hip) and by their caller (rt_api.cpp), so a
+// rt_denoise.hip, rt_temporal.hip, rt_bvh_build.hip, rt_bvh_sah.hip, rt_collapse.hip, rt_refit.hip, rt_query.hip, rt_occlusion.hip) and by their caller (rt_api.cpp), so a
 // definition whose parameter list drifts from its callers' no longer compiles.
 #ifndef RT_KERNELS_H
 #define RT_KERNELS_H
@@ -65,6 +65,11 @@ hipError_t rtk_launch_guides(const DScene *S, const DCamera *C, const DLaunch *P
 // object of each xforms[] record; n <= 0 queues nothing)
 hipError_t rtk_launch_trace(const DScene *S, const int32_t *xf_obj, int64_t n, const rt_ray *rays,
                             rt_ray_hit *hits, hipStream_t stream);
+
+// ---- rt_occlusion.hip: occluded[k] = 1 where something stands in (0.001, t_max] of rays[k], else 0,
+// k in [0, n): one byte each (rt_occlusion.h; n <= 0 queues nothing)
+hipError_t rtk_launch_occluded(const DScene *S, int64_t n, const rt_ray *rays, uint8_t *occluded,
+                               hipStream_t stream);
 
 // ---- rt_denoise.hip: the a-trous filters, one launcher.  Sigmas resolved: > 0 on, <= 0 off; passes < 0: none
 size_t rtk_denoise_workspace_bytes(int W, int H);          // the plain layout

@@ -276,4 +276,5 @@ EXPORTS = (
     "rt_scene_set_transforms", "rt_scene_set_transforms_device", "rt_multi_set_transforms",
     "rt_scene_move_quads", "rt_scene_move_quads_device", "rt_multi_move_quads", "rt_rotate_y_sincos",
     "rt_trace_device", "rt_trace", "rt_multi_trace", "rt_pixel_ray",
+    "rt_occluded_device", "rt_occluded", "rt_multi_occluded", "rt_segment_ray",
 )

@@ -109,6 +109,10 @@ def load():
     L.rt_trace.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     L.rt_multi_trace.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     L.rt_pixel_ray.argtypes = [P(abi.Frame), C.c_double, C.c_double, P(abi.Ray)]
+    L.rt_occluded_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rt_occluded.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.rt_multi_occluded.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.rt_segment_ray.argtypes = [P(C.c_double), P(C.c_double), C.c_double, P(abi.Ray)]
     for name in abi.EXPORTS:
         getattr(L, name).restype = C.c_char_p if name == "rt_last_error" else C.c_int
     if L.rt_abi_version() != abi.RT_ABI_VERSION:

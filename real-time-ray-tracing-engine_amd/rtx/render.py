@@ -94,6 +94,30 @@ def _trace(fn, handle, rays):
     return hits
 
 
+def segment_ray(a, b, time=0.0):
+    """rt_segment_ray for each pair of points: the rays that ask whether b[k]
+    is visible from a[k] (origin a, direction b - a, t_max 0.999).  a, b: [n, 3]
+    (or [3]) float64; a RAY_DTYPE array [n]."""
+    a = np.ascontiguousarray(np.atleast_2d(np.asarray(a, dtype=np.float64)))
+    b = np.ascontiguousarray(np.atleast_2d(np.asarray(b, dtype=np.float64)))
+    if a.shape != b.shape or a.ndim != 2 or a.shape[1] != 3:
+        raise ValueError("a, b: two [n, 3] arrays, not %r and %r" % (a.shape, b.shape))
+    rays = np.empty(len(a), dtype=RAY_DTYPE)
+    fn, D = load().rt_segment_ray, C.POINTER(C.c_double)
+    r = abi.Ray()
+    for k in range(len(a)):
+        check(fn(a[k].ctypes.data_as(D), b[k].ctypes.data_as(D), float(time), C.byref(r)))
+        rays[k:k + 1] = np.frombuffer(bytes(r), dtype=RAY_DTYPE)
+    return rays
+
+
+def _occluded(fn, handle, rays):
+    rays = ray_array(rays)
+    out = np.empty(len(rays), dtype=np.bool_)
+    check(fn(handle, len(rays), C.c_void_p(rays.ctypes.data), C.c_void_p(out.ctypes.data)))
+    return out
+
+
 def camera_frame(cam):
     """Camera::initialize (Camera.cpp:31-73) via rt_camera_setup."""
     f = abi.Frame()
@@ -324,6 +348,25 @@ class Renderer:
         pixel_ray(frame, x, y), one HIT_DTYPE record."""
         return self.trace(pixel_ray(frame, x, y))[0]
 
+    def occluded(self, rays):
+        """rt_occluded: for each ray (as for trace) whether anything stands in
+        (0.001, t_max] of it -- True exactly where trace's record is a hit --
+        as an np.bool_ array [n].  An any-hit search: it stops at the first
+        blocker and never looks beyond t_max.  Synchronous."""
+        return _occluded(self.lib.rt_occluded, self.handle, rays)
+
+    def occluded_device(self, rays_ptr, out_ptr, n, stream_ptr=None):
+        """rt_occluded_device: the same from a device array of n rt_ray into n
+        device bytes (0 or 1; a bool buffer does), asynchronously on
+        `stream_ptr`, after every edit queued before it."""
+        check(self.lib.rt_occluded_device(self.handle, int(n), C.c_void_p(rays_ptr), C.c_void_p(out_ptr),
+                                          C.c_void_p(stream_ptr or 0)))
+
+    def visible(self, a, b, time=0.0):
+        """Whether b[k] is seen from a[k] ([n, 3] each): not occluded along
+        segment_ray(a, b, time).  An np.bool_ array [n]."""
+        return ~self.occluded(segment_ray(a, b, time))
+
 
 class MultiRenderer:
     """rt_multi_*: one device scene per shard (shard k on devices[k % len]),
@@ -385,6 +428,10 @@ class MultiRenderer:
     def trace(self, rays):
         """rt_multi_trace: Renderer.trace on shard 0's scene."""
         return _trace(self.lib.rt_multi_trace, self.handle, rays)
+
+    def occluded(self, rays):
+        """rt_multi_occluded: Renderer.occluded on shard 0's scene."""
+        return _occluded(self.lib.rt_multi_occluded, self.handle, rays)
 
     def rebuild_bvh(self):
         """rt_multi_rebuild_bvh: Renderer.rebuild_bvh on every shard's scene;
