@@ -37,6 +37,7 @@
 #include <set>
 #include <utility>
 
+#include "rt_camq.h"
 #include "rt_kernels.h"
 #include "rt_lds_plan.h"
 #include "rt_path.h"
@@ -47,8 +48,12 @@ namespace {
 using namespace rtp;
 // Idle lanes that trigger a refill while other lanes still trace (measured:
 // 16 for the plain instance, C3 +4 %; the rich instances lose with any delay).
+// The plain flat world pops its camera rays from a queue (rt_camq.h), a refill
+// pass at about a fifth of its former price: re-measured with it, 1 / 4 / 8 /
+// 16 idle lanes x RT_PARK_K 48 / 56 all lie within 3.92-3.97 ms of C2 kernel
+// time, none apart from (16, 48) (profiles/camq_sweep_ab.log).
 #ifndef RT_REGEN_FLAT
-#define RT_REGEN_FLAT 16 // re-measured with RT_PARK_K (profiles/parked_k_ab.log)
+#define RT_REGEN_FLAT 16 // re-measured with RT_PARK_K (profiles/parked_k_ab.log, camq_sweep_ab.log)
 #endif
 #define RT_REGEN_MIN(F) ((F) == F_FLAT ? RT_REGEN_FLAT : (((F) & ~F_BVH4) == 0 ? 16 : 1))
 // Parked shading (the plain flat world, every instance of it: M_ANY, M_DIFFUSE,
@@ -376,6 +381,10 @@ __global__ __launch_bounds__(64 * (PCW ? PCW : block_waves(F))) __attribute__((a
 
   const int n_items = 64 * max(0, s_count);
   int next_item = 0; // wave-uniform head of the tile's work queue
+  // camera rays generated a batch at a time by the whole wave and popped from
+  // LDS (rt_camq.h): the plain flat world, every instance of it
+  constexpr bool kCamq = F == F_FLAT;
+  [[maybe_unused]] int gen_items = 0; // items generated so far (wave-uniform, whole batches)
   PathState ps;
   ps.active = false;
   Key key{P.seed_lo, P.seed_hi, 0, 0};
@@ -393,23 +402,87 @@ __global__ __launch_bounds__(64 * (PCW ? PCW : block_waves(F))) __attribute__((a
       // refill only once enough lanes are idle: camera-ray generation costs the
       // whole wave, however few lanes take new paths
       if (__popcll(idle) < RT_REGEN_MIN(F) && ~idle != 0ull) break;
-      int rank = __popcll(idle & ((1ull << lane) - 1ull));
-      int item = next_item + rank;
-      next_item += __popcll(idle);
-      if (!ps.active && item < n_items) {
+      if constexpr (kCamq) {
+        // ---- camera-ray queue (rt_camq.h): the batches this pop needs and the
+        // ring does not hold yet are generated by the whole wave, lane l making
+        // the ray of pixel slot l in the batch's stratum (wave-uniform: the
+        // stratum's cell and key.sample on the scalar side); then the idle
+        // lanes pop their items.  A ray's arithmetic is camera_ray's, whichever
+        // lane runs it, and the lane that traces and shades an item is the one
+        // that did before: frames keep their bits.
+        static_assert(BW == 1, "the camera-ray queue is one wave's");
+        __shared__ double camq[rtq::kComps][rtq::kEntries];
         const DCamera &Cr = C;
-        int slot = item & 63;
-        int i = x0 + (slot & 7), j = y0 + (slot >> 3);
-        if (i < Cr.W && j < P.row_end) {
-          ps.slot = slot;
-          ps.sample = s_first + (item >> 6);
-          key.pixel = (uint32_t)(j * Cr.W + i);
-          key.sample = (uint32_t)ps.sample;
-          ps.ray = camera_ray<RT_KB_F(F), RT_KCONST_MODE(F)>(Cr, key, i, j, ps.sample);
-          ps.T = v3(1.0, 1.0, 1.0);
-          ps.bounce = 0;
-          ps.active = Cr.max_depth > 0;
-          if (STATS) n_samples++;
+        const bool lens = !(Cr.defocus_angle <= 0); // camera_ray_jt's branch: the origin is drawn
+        // this lane's rank among the idle lanes (mbcnt: no lane mask held in registers)
+        const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
+        const int item = next_item + rank;
+        // wave-uniform by construction; said so, so that the loop below is a
+        // scalar branch and gen_items and the batch's stratum stay in SGPRs
+        const int need = __builtin_amdgcn_readfirstlane(rtq::camq_need(next_item, __popcll(idle), n_items));
+        while (rtq::camq_generate(gen_items, need)) { // wave-uniform: all 64 lanes
+          // the camera read afresh from the kernarg segment: its fields are not
+          // held in SGPRs across the path loop (held, they spill into the trace)
+          const DCamera Cg = camera_fields<true>(C);
+          const int gk = __builtin_amdgcn_readfirstlane(s_first + rtq::camq_batch(gen_items));
+          const int gi = x0 + (lane & 7), gj = y0 + (lane >> 3);
+          const Key gkey{P.seed_lo, P.seed_hi, (uint32_t)(gj * Cg.W + gi), (uint32_t)gk};
+          const Ray gr = camera_ray<RT_KB_F(F), RT_KCONST_MODE(F)>(Cg, gkey, gi, gj, gk);
+          const int e = rtq::camq_write_entry(gen_items, lane);
+          camq[0][e] = gr.d.x;
+          camq[1][e] = gr.d.y;
+          camq[2][e] = gr.d.z;
+          camq[3][e] = gr.tm;
+          if (lens) {
+            camq[4][e] = gr.o.x;
+            camq[5][e] = gr.o.y;
+            camq[6][e] = gr.o.z;
+          }
+          gen_items += rtq::kBatch;
+        }
+        // one wave's LDS operations complete in order: the compiler must only
+        // keep the pop's reads after the batch's writes
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        next_item += __popcll(idle);
+        if (!ps.active && item < n_items) {
+          int slot = item & 63;
+          int i = x0 + (slot & 7), j = y0 + (slot >> 3);
+          if (i < Cr.W && j < P.row_end) { // an item outside is consumed and leaves its lane idle
+            const int e = rtq::camq_read_entry(item);
+            ps.slot = slot;
+            ps.sample = s_first + (item >> 6);
+            key.pixel = (uint32_t)(j * Cr.W + i);
+            key.sample = (uint32_t)ps.sample;
+            ps.ray.d = v3(camq[0][e], camq[1][e], camq[2][e]);
+            ps.ray.tm = camq[3][e];
+            ps.ray.o = lens ? v3(camq[4][e], camq[5][e], camq[6][e]) : ld3(Cr.center);
+            ps.T = v3(1.0, 1.0, 1.0);
+            ps.bounce = 0;
+            ps.active = Cr.max_depth > 0;
+            if (STATS) n_samples++;
+          }
+        }
+      } else {
+        int rank = __popcll(idle & ((1ull << lane) - 1ull));
+        int item = next_item + rank;
+        next_item += __popcll(idle);
+        if (!ps.active && item < n_items) {
+          const DCamera &Cr = C;
+          int slot = item & 63;
+          int i = x0 + (slot & 7), j = y0 + (slot >> 3);
+          if (i < Cr.W && j < P.row_end) {
+            ps.slot = slot;
+            ps.sample = s_first + (item >> 6);
+            key.pixel = (uint32_t)(j * Cr.W + i);
+            key.sample = (uint32_t)ps.sample;
+            ps.ray = camera_ray<RT_KB_F(F), RT_KCONST_MODE(F)>(Cr, key, i, j, ps.sample);
+            ps.T = v3(1.0, 1.0, 1.0);
+            ps.bounce = 0;
+            ps.active = Cr.max_depth > 0;
+            if (STATS) n_samples++;
+          }
         }
       }
     }
