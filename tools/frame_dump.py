@@ -33,8 +33,14 @@ def compare(pa, pb):
     if not pa.endswith(".npz"):
         same = same_bits(x, y)
         diff = 0 if same else int(np.count_nonzero(x.view(np.uint64) != y.view(np.uint64)))
+        rel = None
+        if x.shape == y.shape:  # relative to the larger of the two, 0 where both are 0
+            with np.errstate(invalid="ignore", divide="ignore"):
+                m = np.maximum(np.abs(x), np.abs(y))
+                rel = float(np.nanmax(np.where(m > 0, np.abs(x - y) / m, 0.0)))
         print({"bit_identical": bool(same), "differing_doubles": diff, "shape": list(x.shape),
-               "max_abs_diff": float(np.nanmax(np.abs(x - y))) if x.shape == y.shape else None})
+               "max_abs_diff": float(np.nanmax(np.abs(x - y))) if x.shape == y.shape else None,
+               "max_rel_diff": rel, "max_rel_diff_log2": float(np.log2(rel)) if rel else None})
         return same
     differing = sorted(k for k in set(x.files) | set(y.files)
                        if k not in x.files or k not in y.files or not same_bits(x[k], y[k]))
