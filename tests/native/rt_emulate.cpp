@@ -22,10 +22,12 @@ using namespace rtp;
 
 namespace {
 
-template <unsigned F>
+// STATS: the counted twin (segment<true, F>): `cnt` collects what the paths of
+// this pixel do, `segs` their segments
+template <bool STATS, unsigned F>
 void trace_pixel(const DScene &S, const DCamera &C, const rt_render_params &p, int i, int j,
-                 int s0, int s1, int *stk, const DNode *ln, double acc[3]) {
-  Counters cnt{};
+                 int s0, int s1, int *stk, const DNode *ln, double acc[3], Counters &cnt,
+                 uint64_t &segs) {
   for (int k = s0; k < s1; ++k) {
     Key key{(uint32_t)p.seed, (uint32_t)(p.seed >> 32), (uint32_t)(j * C.W + i), (uint32_t)k};
     PathState ps;
@@ -34,7 +36,8 @@ void trace_pixel(const DScene &S, const DCamera &C, const rt_render_params &p, i
     ps.bounce = 0;
     ps.active = C.max_depth > 0;
     while (ps.active) {
-      bool cont = segment<false, F>(S, C, ps, key, stk, ln, cnt);
+      if (STATS) ++segs;
+      bool cont = segment<STATS, F>(S, C, ps, key, stk, ln, cnt);
       if (!cont) {
         acc[0] += ps.T.x;
         acc[1] += ps.T.y;
@@ -46,18 +49,19 @@ void trace_pixel(const DScene &S, const DCamera &C, const rt_render_params &p, i
 }
 
 typedef void (*PixelFn)(const DScene &, const DCamera &, const rt_render_params &, int, int, int,
-                        int, int *, const DNode *, double *);
-template <unsigned... Fs>
+                        int, int *, const DNode *, double *, Counters &, uint64_t &);
+template <bool STATS, unsigned... Fs>
 constexpr std::array<PixelFn, sizeof...(Fs)> pixel_fns(std::integer_sequence<unsigned, Fs...>) {
-  return {trace_pixel<Fs>...};
+  return {trace_pixel<STATS, Fs>...};
 }
-// one per kernel instance (rt_kernel.hip render_table)
-constexpr auto kFns = pixel_fns(std::make_integer_sequence<unsigned, F_ALL + 1>{});
+// one per kernel instance (rt_kernel.hip render_table), and the counted twins
+constexpr auto kFns = pixel_fns<false>(std::make_integer_sequence<unsigned, F_ALL + 1>{});
+constexpr auto kFnsStats = pixel_fns<true>(std::make_integer_sequence<unsigned, F_ALL + 1>{});
 
-} // namespace
-
-extern "C" int emu_render(const rt_scene_desc *desc, const rt_frame *f, const rt_render_params *p,
-                          int features, double *out) {
+// emu_render (stats == nullptr, the plain instance) and emu_render_stats (the
+// counted instance; `out` may be null)
+int render_host(const rt_scene_desc *desc, const rt_frame *f, const rt_render_params *p,
+                int features, double *out, rt_path_stats *stats) {
   rtx::HostScene H;
   std::string err;
   if (rtx::compile_scene(desc, H, err) != RT_OK) return -1;
@@ -113,18 +117,60 @@ extern "C" int emu_render(const rt_scene_desc *desc, const rt_frame *f, const rt
   std::vector<int> stack(std::max(RT_STACK_DEPTH, RT_STACK_DEPTH4) * 64);
   // the instance the library would pick: the caller's feature bits plus F_FLAT
   // for a flat world, F_BVH4 for a collapsed tree (rt_api.cpp)
-  PixelFn fn = kFns[(features & 15) | (H.root_is_leaf ? F_FLAT : 0u) | (bvh4 ? F_BVH4 : 0u)];
+  const unsigned inst = (features & 15) | (H.root_is_leaf ? F_FLAT : 0u) | (bvh4 ? F_BVH4 : 0u);
+  PixelFn fn = stats ? kFnsStats[inst] : kFns[inst];
+  Counters cnt{};
+  uint64_t segs = 0, samples = 0;
   for (int j = r0; j < r1; ++j)
     for (int i = 0; i < C.W; ++i) {
       double acc[3] = {0, 0, 0};
-      fn(S, C, *p, i, j, s0, s1, stack.data(), ln, acc);
+      fn(S, C, *p, i, j, s0, s1, stack.data(), ln, acc, cnt, segs);
+      // the kernel counts a sample per in-image item it takes, whatever max_depth is
+      samples += (uint64_t)std::max(0, s1 - s0);
+      if (!out) continue;
       double sc = (p->output == RT_OUT_SCALED) ? C.scale : 1.0;
       double *o = out + 3 * ((size_t)(j - r0) * C.W + i);
       o[0] = (p->output == RT_OUT_SCALED) ? sc * acc[0] : acc[0];
       o[1] = (p->output == RT_OUT_SCALED) ? sc * acc[1] : acc[1];
       o[2] = (p->output == RT_OUT_SCALED) ? sc * acc[2] : acc[2];
     }
+  if (stats) {
+    *stats = rt_path_stats{};
+    stats->samples = samples;
+    stats->segments = segs;
+    stats->node_visits = cnt.nodes;
+    stats->sphere_tests = cnt.spheres;
+    stats->quad_tests = cnt.quads;
+    stats->other_tests = cnt.other;
+    stats->light_tests = cnt.light;
+    stats->shade_events = cnt.shade;
+    stats->wave_node_iters = cnt.wnode;
+    stats->wave_leaf_iters = cnt.wleaf;
+    stats->wave_shade_iters = cnt.wshade;
+    stats->noise_evals = cnt.noise;
+    stats->wave_noise_iters = cnt.wnoise;
+    stats->medium_box_tests = cnt.mbox;
+    stats->medium_box_deferred = cnt.mbox_fb;
+  }
   return 0;
+}
+
+} // namespace
+
+extern "C" int emu_render(const rt_scene_desc *desc, const rt_frame *f, const rt_render_params *p,
+                          int features, double *out) {
+  return render_host(desc, f, p, features, out, nullptr);
+}
+
+// The counted twin of emu_render (tests/test_material_worlds_gpu.py): the same
+// loop over segment<true, F>, one lane at a time.  `stats` gets the counters
+// that depend on the paths alone (a "wave" here is one lane: the wave_*
+// fields count per path; cycles, trips and the traversal model stay 0).
+extern "C" int emu_render_stats(const rt_scene_desc *desc, const rt_frame *f,
+                                const rt_render_params *p, int features, double *out,
+                                rt_path_stats *stats) {
+  if (!stats) return -3;
+  return render_host(desc, f, p, features, out, stats);
 }
 
 // The 4-wide collapse of the world BVH of `desc` (tests/test_emulator.py):
