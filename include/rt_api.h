@@ -1200,6 +1200,90 @@ int rt_multi_occluded(rt_multi *multi, int64_t n, const rt_ray *rays, uint8_t *o
    RT_ERR_INVALID: a null pointer. */
 int rt_segment_ray(const double a[3], const double b[3], double time, rt_ray *ray);
 
+/* ---- radiance queries (four functions and one struct added under ABI 5: no
+   struct or signature above changed) -----------------------------------------
+   rt_trace asks for the closest surface along a ray and rt_occluded for any
+   blocker; these calls ask what a path tracer exists to answer: how much
+   light arrives along the ray (csrc/rt_radiance.h, rt_radiance.hip; DESIGN.md
+   "Radiance queries").  Light probes, lightmap texels, a fisheye, orthographic,
+   panoramic or stereo camera, a renderer that brings its own primary rays:
+   each makes its rt_ray array and gets this library's light transport.
+
+   Per sample.  Sample s of ray k is the render's own path: it starts as
+   Ray{origin, direction, time} with weight 1 at bounce 0 and runs the
+   render's integrator (rt_path.h segment) until it ends, with the RNG key
+   Key{seed; first_key + k, first_sample + s} where the render has
+   Key{seed; pixel, stratum}.  The range (0.001, inf) in units of `direction`,
+   the media's free-flight draws, light sampling, the max_depth rule and
+   miss -> background are the render's; the sample's value is the path's
+   terminal weight.  t_max is not read.  The kernel instance is the one the
+   scene's renders run (the feature set of rt_scene_info.features, and the
+   Lambertian-only form of a plain flat diffuse-only world), with nodes and
+   Perlin tables read from memory.
+
+   Per ray.  rgb[k] = +0.0, or its current value when `accumulate`, plus the
+   samples, added in ascending s, each channel separately: a raw sum by the
+   RT_OUT_SUM convention, the caller scales.  The result is a property of the
+   ray, its key and the scene's tables alone: it does not depend on the rays
+   around it, on its position in a launch (first_key + k names it), on the tree
+   (host-built, device-built, refitted, rebuilt, binary or 4-wide), or on where
+   a sample range is split -- samples [0, 4) in one call give the bytes of
+   [0, 2) followed by [2, 4) with accumulate.
+
+   Bad rays.  A ray with a zero direction, or with a NaN or infinite origin,
+   direction or time component (rt_trace's test, without its rule for t_max:
+   t_max is ignored even if NaN), contributes nothing and draws nothing: its
+   rgb is 0, or is left as it was under `accumulate`.
+
+   With rt_camera_rays below, first_key = row_begin * image_width,
+   first_sample = stratum and samples = 1 re-create one stratum of rt_render
+   with RT_OUT_SUM, bit for bit. */
+typedef struct rt_radiance_params {
+  uint64_t seed;          /* the render's seed: Key{k0,k1} = (lo, hi) */
+  uint32_t first_key;     /* Key.pixel of ray k is first_key + k (mod 2^32) */
+  int32_t  first_sample;  /* Key.sample of a ray's s-th sample is first_sample + s */
+  int32_t  samples;       /* samples per ray, >= 0 */
+  int32_t  max_depth;     /* the frame's max_depth; <= 0: every sample is 0 */
+  int32_t  accumulate;    /* 0: rgb[k] = sum; 1: rgb[k] += the samples, in order */
+  int32_t  _reserved;     /* 0 */
+  rt_vec3  background;    /* what a miss returns (rt_frame.background) */
+} rt_radiance_params; /* 56 B */
+
+/* device_rgb[3k .. 3k+2] = the sum of device_rays[k] for k in [0, n): every
+   one written exactly once with plain stores, nothing else is written.  Both
+   arrays are device memory of the scene's device, 8-byte aligned.
+   Asynchronous on hip_stream (NULL = the HIP null stream); a link of the
+   scene's launch chain like rt_trace_device: it sees every edit queued before
+   it, and rt_scene_destroy waits for it.  Uses none of the scene's scratch
+   and allocates nothing.  n = 0, and samples = 0 with accumulate, queue
+   nothing and return RT_OK.
+   RT_ERR_INVALID, before anything is queued: null params; non-zero
+   _reserved; samples < 0, first_sample < 0, or first_sample + samples above
+   INT32_MAX; n < 0; n above 2^32 (keys must be distinct within a call); a
+   null array with n > 0; a null scene. */
+int rt_radiance_device(rt_scene *scene, int64_t n, const rt_ray *device_rays, const rt_radiance_params *params,
+                       double *device_rgb, void *hip_stream);
+
+/* The same with host arrays: staged through device memory on the scene's own
+   stream (with accumulate, rgb goes up too); the sums are in `rgb` on return. */
+int rt_radiance(rt_scene *scene, int64_t n, const rt_ray *rays, const rt_radiance_params *params, double *rgb);
+
+/* rt_radiance on shard 0's scene (the shards hold one description). */
+int rt_multi_radiance(rt_multi *multi, int64_t n, const rt_ray *rays, const rt_radiance_params *params,
+                      double *rgb);
+
+/* The render's own camera ray for every pixel of rows [row_begin, row_end)
+   (0, 0: the whole frame), row-major: rays[(j - row_begin) * image_width + i]
+   is the ray rt_render traces for stratum `stratum` of pixel (i, j) under
+   `seed` -- its jitter inside the stratum's cell, its defocus origin and its
+   ray time, from Key{seed; j * image_width + i, stratum} -- with
+   t_max = +inf.  Useful on its own (another integrator on the render's rays)
+   and with rt_radiance above.  Host only: needs no scene and no device.
+   RT_ERR_INVALID: a null pointer, a frame rt_render would refuse, rows outside
+   the frame, stratum outside [0, sqrt_spp^2). */
+int rt_camera_rays(const rt_frame *frame, uint64_t seed, int32_t stratum, int32_t row_begin, int32_t row_end,
+                   rt_ray *rays);
+
 /* ---- guided sampling (one function added under ABI 5: no struct or signature
    above changed) ------------------------------------------------------------
    rt_adaptive_select_device retires a tile by the new pose's own batch

@@ -1137,7 +1137,8 @@ int rt_trace(rt_scene *s, int64_t n, const rt_ray *rays, rt_ray_hit *hits) {
   if (rc || n == 0) return rc;
   DeviceGuard g(s->device);
   const size_t ray_bytes = sizeof(rt_ray) * (size_t)n, hit_bytes = sizeof(rt_ray_hit) * (size_t)n;
-  // only this function and rt_occluded use trace_buf, on the scene's stream, and each synchronises before it returns
+  // only this function, rt_occluded and rt_radiance use trace_buf, on the scene's stream, and each synchronises
+  // before it returns
   if ((rc = grow(s, s->trace_buf, s->trace_bytes, align256(ray_bytes) + hit_bytes, Idle::Already,
                  "hipMallocFromPoolAsync query")))
     return rc;
@@ -1219,6 +1220,89 @@ int rt_segment_ray(const double a[3], const double b[3], double time, rt_ray *ra
   }
   ray->time = time;
   ray->t_max = 0.999; // the search starts at 0.001: both ends' own surfaces are skipped alike
+  return RT_OK;
+}
+
+// ----------------------------------------------------------- radiance queries
+// One launch of the radiance kernel (rt_radiance.hip) on `st`: a link of the
+// scene's chain exactly as trace_on_stream is.  The scene comes last in the
+// checks, as in trace_check: every other refusal needs no scene.
+static int radiance_check(const rt_scene *s, int64_t n, const void *rays, const rt_radiance_params *p,
+                          const void *rgb) {
+  if (!p) return set_err(RT_ERR_INVALID, "null radiance params");
+  if (p->_reserved != 0) return set_err(RT_ERR_INVALID, "rt_radiance_params._reserved must be 0");
+  if (p->samples < 0) return set_err(RT_ERR_INVALID, "negative sample count");
+  if (p->first_sample < 0) return set_err(RT_ERR_INVALID, "negative first_sample");
+  if ((int64_t)p->first_sample + p->samples > 0x7fffffffll)
+    return set_err(RT_ERR_INVALID, "first_sample + samples overflows int32");
+  if (n < 0) return set_err(RT_ERR_INVALID, "negative ray count");
+  if (n > ((int64_t)1 << 32))
+    return set_err(RT_ERR_INVALID, "more than 2^32 rays in one call: their keys would repeat");
+  if (n > 0 && (!rays || !rgb)) return set_err(RT_ERR_INVALID, "null ray or rgb array");
+  if (!s) return set_err(RT_ERR_INVALID, "null scene");
+  return RT_OK;
+}
+// nothing to queue: no ray, or nothing to add onto what the buffer holds
+static bool radiance_empty(int64_t n, const rt_radiance_params *p) {
+  return n == 0 || (p->samples == 0 && p->accumulate);
+}
+static int radiance_on_stream(rt_scene *s, int64_t n, const rt_ray *d_rays, const rt_radiance_params *p,
+                              double *d_rgb, hipStream_t st) {
+  DCamera C{}; // what segment and advance read of it: the background and the depth budget
+  C.bg[0] = p->background.x, C.bg[1] = p->background.y, C.bg[2] = p->background.z;
+  C.max_depth = p->max_depth;
+  int rc = order_after_last(s, st);
+  if (rc) return rc;
+  hipError_t e = rtk_launch_radiance(&s->ds, &C, p, n, d_rays, d_rgb, st);
+  if (e != hipSuccess) return hip_err(e, "radiance kernel launch");
+  return mark_last(s, st);
+}
+
+int rt_radiance_device(rt_scene *s, int64_t n, const rt_ray *device_rays, const rt_radiance_params *p,
+                       double *device_rgb, void *hip_stream) {
+  int rc = radiance_check(s, n, device_rays, p, device_rgb);
+  if (rc || radiance_empty(n, p)) return rc;
+  DeviceGuard g(s->device);
+  return radiance_on_stream(s, n, device_rays, p, device_rgb, (hipStream_t)hip_stream);
+}
+
+int rt_radiance(rt_scene *s, int64_t n, const rt_ray *rays, const rt_radiance_params *p, double *rgb) {
+  int rc = radiance_check(s, n, rays, p, rgb);
+  if (rc || radiance_empty(n, p)) return rc;
+  DeviceGuard g(s->device);
+  const size_t ray_bytes = sizeof(rt_ray) * (size_t)n, rgb_bytes = 3 * sizeof(double) * (size_t)n;
+  // trace_buf is rt_trace's, rt_occluded's and this function's: each uses it on
+  // the scene's stream and synchronises before it returns
+  if ((rc = grow(s, s->trace_buf, s->trace_bytes, align256(ray_bytes) + rgb_bytes, Idle::Already,
+                 "hipMallocFromPoolAsync radiance query")))
+    return rc;
+  const rt_ray *d_rays = (const rt_ray *)s->trace_buf;
+  double *d_rgb = (double *)(s->trace_buf + align256(ray_bytes));
+  hipError_t e = hipMemcpyAsync(s->trace_buf, rays, ray_bytes, hipMemcpyHostToDevice, s->stream);
+  if (e == hipSuccess && p->accumulate) e = hipMemcpyAsync(d_rgb, rgb, rgb_bytes, hipMemcpyHostToDevice, s->stream);
+  if (e == hipSuccess) {
+    rc = radiance_on_stream(s, n, d_rays, p, d_rgb, s->stream);
+    if (rc == RT_OK) e = hipMemcpyAsync(rgb, d_rgb, rgb_bytes, hipMemcpyDeviceToHost, s->stream);
+  }
+  const hipError_t es = hipStreamSynchronize(s->stream);
+  if (rc) return rc;
+  if (e != hipSuccess) return hip_err(e, "radiance query copy");
+  return es == hipSuccess ? RT_OK : hip_err(es, "radiance kernel");
+}
+
+int rt_camera_rays(const rt_frame *f, uint64_t seed, int32_t stratum, int32_t row_begin, int32_t row_end,
+                   rt_ray *rays) {
+  if (!rays) return set_err(RT_ERR_INVALID, "null ray array");
+  DCamera C;
+  int rc = to_device_camera(f, C);
+  if (rc) return rc;
+  if (row_begin == 0 && row_end == 0) row_end = C.H; // rt_render_params' whole frame
+  if (row_begin < 0 || row_end > C.H || row_end <= row_begin)
+    return set_err(RT_ERR_INVALID, "row range outside the image");
+  if (stratum < 0 || stratum >= (int64_t)C.sqrt_spp * C.sqrt_spp)
+    return set_err(RT_ERR_INVALID, "stratum outside [0, sqrt_spp^2)");
+  if ((int64_t)C.W * C.H > 0xFFFFFFFFll) return set_err(RT_ERR_UNSUPPORTED, "image too large for 32-bit pixel keys");
+  rtk_camera_rays_host(&C, seed, stratum, row_begin, row_end, rays);
   return RT_OK;
 }
 
@@ -2167,6 +2251,10 @@ int rt_multi_trace(rt_multi *m, int64_t n, const rt_ray *rays, rt_ray_hit *hits)
 
 int rt_multi_occluded(rt_multi *m, int64_t n, const rt_ray *rays, uint8_t *occluded) {
   return rt_occluded(m && !m->scenes.empty() ? m->scenes[0] : nullptr, n, rays, occluded); // as rt_multi_trace
+}
+
+int rt_multi_radiance(rt_multi *m, int64_t n, const rt_ray *rays, const rt_radiance_params *p, double *rgb) {
+  return rt_radiance(m && !m->scenes.empty() ? m->scenes[0] : nullptr, n, rays, p, rgb); // as rt_multi_trace
 }
 
 int rt_multi_shard_ms(rt_multi *m, double *ms) {

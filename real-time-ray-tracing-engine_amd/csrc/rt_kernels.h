@@ -1,6 +1,6 @@
 // rt_kernels.h — every rtk_* launcher, declared once: included by the files
 // that define them (rt_kernel.hip, rt_frame.hip, rt_adaptive.hip, rt_guides.hip,
-// rt_denoise.hip, rt_temporal.hip, rt_bvh_build.hip, rt_bvh_sah.hip, rt_collapse.hip, rt_refit.hip, rt_query.hip, rt_occlusion.hip) and by their caller (rt_api.cpp), so a
+// rt_denoise.hip, rt_temporal.hip, rt_bvh_build.hip, rt_bvh_sah.hip, rt_collapse.hip, rt_refit.hip, rt_query.hip, rt_occlusion.hip, rt_radiance.hip) and by their caller (rt_api.cpp), so a
 // definition whose parameter list drifts from its callers' no longer compiles.
 #ifndef RT_KERNELS_H
 #define RT_KERNELS_H
@@ -70,6 +70,15 @@ hipError_t rtk_launch_trace(const DScene *S, const int32_t *xf_obj, int64_t n, c
 // k in [0, n): one byte each (rt_occlusion.h; n <= 0 queues nothing)
 hipError_t rtk_launch_occluded(const DScene *S, int64_t n, const rt_ray *rays, uint8_t *occluded,
                                hipStream_t stream);
+
+// ---- rt_radiance.hip: rgb[k] (3 doubles) = (accumulate: itself) + the p->samples path-traced samples of
+// rays[k], k in [0, n) (rt_radiance.h; C: bg and max_depth are read; p checked by the caller; n <= 0
+// queues nothing)
+hipError_t rtk_launch_radiance(const DScene *S, const DCamera *C, const rt_radiance_params *p, int64_t n,
+                               const rt_ray *rays, double *rgb, hipStream_t stream);
+// host only: rays[(j - row_begin) * W + i] = the render's camera ray of stratum `stratum` of pixel (i, j)
+void rtk_camera_rays_host(const DCamera *C, uint64_t seed, int32_t stratum, int32_t row_begin, int32_t row_end,
+                          rt_ray *rays);
 
 // ---- rt_denoise.hip: the a-trous filters, one launcher.  Sigmas resolved: > 0 on, <= 0 off; passes < 0: none
 size_t rtk_denoise_workspace_bytes(int W, int H);          // the plain layout

@@ -244,6 +244,13 @@ class RayHit(C.Structure):
                 ("material", C.c_int32), ("front", C.c_int32)]
 
 
+class RadianceParams(C.Structure):
+    """rt_radiance_params (56 B)."""
+    _fields_ = [("seed", C.c_uint64), ("first_key", C.c_uint32), ("first_sample", C.c_int32),
+                ("samples", C.c_int32), ("max_depth", C.c_int32), ("accumulate", C.c_int32),
+                ("_reserved", C.c_int32), ("background", Vec3)]
+
+
 def tuning(t=None):
     """A Tuning from None (the default), a Tuning, or a dict of its fields."""
     if t is None or isinstance(t, Tuning):
@@ -277,4 +284,5 @@ EXPORTS = (
     "rt_scene_move_quads", "rt_scene_move_quads_device", "rt_multi_move_quads", "rt_rotate_y_sincos",
     "rt_trace_device", "rt_trace", "rt_multi_trace", "rt_pixel_ray",
     "rt_occluded_device", "rt_occluded", "rt_multi_occluded", "rt_segment_ray",
+    "rt_radiance_device", "rt_radiance", "rt_multi_radiance", "rt_camera_rays",
 )

@@ -113,6 +113,10 @@ def load():
     L.rt_occluded.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     L.rt_multi_occluded.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     L.rt_segment_ray.argtypes = [P(C.c_double), P(C.c_double), C.c_double, P(abi.Ray)]
+    L.rt_radiance_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, P(abi.RadianceParams), C.c_void_p, C.c_void_p]
+    L.rt_radiance.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, P(abi.RadianceParams), C.c_void_p]
+    L.rt_multi_radiance.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, P(abi.RadianceParams), C.c_void_p]
+    L.rt_camera_rays.argtypes = [P(abi.Frame), C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
     for name in abi.EXPORTS:
         getattr(L, name).restype = C.c_char_p if name == "rt_last_error" else C.c_int
     if L.rt_abi_version() != abi.RT_ABI_VERSION:

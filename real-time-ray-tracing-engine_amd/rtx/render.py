@@ -118,6 +118,43 @@ def _occluded(fn, handle, rays):
     return out
 
 
+def camera_rays(frame, seed, stratum, rows=(0, 0)):
+    """rt_camera_rays: the render's own camera ray of stratum `stratum` for
+    every pixel of rows [rows[0], rows[1]) ((0, 0): the whole frame), row-major
+    -- jitter, defocus origin and ray time from Key{seed; j * W + i, stratum},
+    t_max = inf.  A RAY_DTYPE array [rows * W]."""
+    r0, r1 = int(rows[0]), int(rows[1])
+    n_rows = frame.image_height if (r0 == 0 and r1 == 0) else r1 - r0
+    rays = np.empty(max(0, n_rows) * max(0, frame.image_width), dtype=RAY_DTYPE)
+    check(load().rt_camera_rays(C.byref(frame), int(seed) & 0xFFFFFFFFFFFFFFFF, int(stratum), r0, r1,
+                                C.c_void_p(rays.ctypes.data)))
+    return rays
+
+
+def radiance_params(samples=1, seed=0, max_depth=50, background=(0, 0, 0), first_key=0, first_sample=0,
+                    accumulate=0):
+    """An abi.RadianceParams (rt_radiance_params)."""
+    p = abi.RadianceParams()
+    p.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    p.first_key = int(first_key) & 0xFFFFFFFF
+    p.first_sample, p.samples, p.max_depth = int(first_sample), int(samples), int(max_depth)
+    p.accumulate = int(accumulate)
+    p.background = abi.Vec3.of(background.tolist() if isinstance(background, abi.Vec3) else background)
+    return p
+
+
+def _radiance(fn, handle, rays, out, **kw):
+    rays = ray_array(rays)
+    accumulate = out is not None  # a caller's array is added onto
+    if out is None:
+        out = np.empty((len(rays), 3), dtype=np.float64)
+    if out.dtype != np.float64 or not out.flags.c_contiguous or out.shape != (len(rays), 3):
+        raise ValueError("out: a C-contiguous float64 array [%d, 3]" % len(rays))
+    p = radiance_params(accumulate=1 if accumulate else 0, **kw)
+    check(fn(handle, len(rays), C.c_void_p(rays.ctypes.data), C.byref(p), C.c_void_p(out.ctypes.data)))
+    return out
+
+
 def camera_frame(cam):
     """Camera::initialize (Camera.cpp:31-73) via rt_camera_setup."""
     f = abi.Frame()
@@ -367,6 +404,30 @@ class Renderer:
         segment_ray(a, b, time).  An np.bool_ array [n]."""
         return ~self.occluded(segment_ray(a, b, time))
 
+    def radiance(self, rays, samples=1, seed=0, max_depth=50, background=(0, 0, 0), first_key=0,
+                 first_sample=0, out=None):
+        """rt_radiance: the path-traced light arriving along each ray (as for
+        trace; t_max is not read) as a float64 array [n, 3] of raw sums over
+        `samples` samples -- sample s of ray k is the render's own path under
+        Key{seed; first_key + k, first_sample + s}, with the render's
+        max_depth rule and `background` for a miss.  The caller scales.  `out`:
+        an [n, 3] float64 array the samples are added onto (accumulate); it
+        is returned.  With camera_rays(frame, seed, k), first_sample=k and the
+        frame's max_depth and background this is stratum k of
+        render(..., output=RT_OUT_SUM).  Synchronous."""
+        return _radiance(self.lib.rt_radiance, self.handle, rays, out, samples=samples, seed=seed,
+                         max_depth=max_depth, background=background, first_key=first_key,
+                         first_sample=first_sample)
+
+    def radiance_device(self, rays_ptr, rgb_ptr, n, samples=1, seed=0, max_depth=50, background=(0, 0, 0),
+                        first_key=0, first_sample=0, accumulate=0, stream_ptr=None):
+        """rt_radiance_device: the same from a device array of n rt_ray into a
+        device array of 3 n doubles (written, or added onto with accumulate),
+        asynchronously on `stream_ptr`, after every edit queued before it."""
+        p = radiance_params(samples, seed, max_depth, background, first_key, first_sample, accumulate)
+        check(self.lib.rt_radiance_device(self.handle, int(n), C.c_void_p(rays_ptr), C.byref(p),
+                                          C.c_void_p(rgb_ptr), C.c_void_p(stream_ptr or 0)))
+
 
 class MultiRenderer:
     """rt_multi_*: one device scene per shard (shard k on devices[k % len]),
@@ -432,6 +493,13 @@ class MultiRenderer:
     def occluded(self, rays):
         """rt_multi_occluded: Renderer.occluded on shard 0's scene."""
         return _occluded(self.lib.rt_multi_occluded, self.handle, rays)
+
+    def radiance(self, rays, samples=1, seed=0, max_depth=50, background=(0, 0, 0), first_key=0,
+                 first_sample=0, out=None):
+        """rt_multi_radiance: Renderer.radiance on shard 0's scene."""
+        return _radiance(self.lib.rt_multi_radiance, self.handle, rays, out, samples=samples,
+                         seed=seed, max_depth=max_depth, background=background, first_key=first_key,
+                         first_sample=first_sample)
 
     def rebuild_bvh(self):
         """rt_multi_rebuild_bvh: Renderer.rebuild_bvh on every shard's scene;

@@ -1,0 +1,9 @@
+# TEST-ONLY host build of the radiance kernel's per-ray source:
+#   build/libradiance_emu.so  csrc/rt_radiance.h by g++, see rt_radiance_emu.cpp
+# (make -C tests/native -f radiance.mk; written under a temporary name and
+# renamed, as in Makefile: parallel test workers may run this at once)
+CXX ?= g++
+PKG := ../../real-time-ray-tracing-engine_amd
+build/libradiance_emu.so: rt_radiance_emu.cpp $(PKG)/csrc/rt_radiance.h $(PKG)/csrc/rt_query.h $(PKG)/csrc/rt_path.h $(PKG)/csrc/rt_layout.h $(PKG)/csrc/rt_scene.cpp $(PKG)/csrc/rt_scene.h $(PKG)/csrc/rt_collapse.h $(PKG)/csrc/rt_plan.h ../../include/rt_api.h
+	@mkdir -p build
+	$(CXX) -std=c++17 -O2 -ffp-contract=off -fPIC -shared -w -o $@.$$$$ rt_radiance_emu.cpp $(PKG)/csrc/rt_scene.cpp && mv -f $@.$$$$ $@
