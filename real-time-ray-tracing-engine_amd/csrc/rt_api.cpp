@@ -29,6 +29,10 @@
 #include "rt_plan.h"
 #include "rt_live_check.h"
 #include "rt_scene.h"
+// radiance_camera; rt_path.h's few non-inline host functions are rt_kernel.o's to export
+#pragma clang attribute push(__attribute__((internal_linkage)), apply_to = function)
+#include "rt_radiance.h"
+#pragma clang attribute pop
 
 struct rt_scene {
   int device = 0;
@@ -126,7 +130,7 @@ struct rt_scene {
   // Ray queries (rt_trace*).  `xf_obj`: per xforms[] record the object it came
   // from (rtx::xform_objects), uploaded at creation -- its own allocation, so
   // the block and the DScene are what they were; `trace_buf` stages the host
-  // variant's rays and hits.
+  // variants' rays and results (query_from_host).
   int32_t *xf_obj = nullptr;
   char *trace_buf = nullptr;
   size_t trace_bytes = 0;
@@ -675,7 +679,7 @@ int rt_scene_create_tuned(const rt_scene_desc *desc, int32_t device, const rt_tu
   int rc = compile_and_validate(desc, device, tune, H);
   if (rc != RT_OK) return rc;
   DeviceGuard g(device);
-  const bool want4 = desc->bvh_arity == 4 || (desc->bvh_arity == 0 && H.items.size() >= (size_t)rtx::kBvh4Min);
+  const bool want4 = rtx::wants_bvh4(desc, H);
   ScenePtr s;
   int builder = RT_BVH_HOST;
   RtkLdsPlan plan{};
@@ -1107,52 +1111,115 @@ int rt_render_guides_device(rt_scene *s, const rt_frame *f, const rt_render_para
 }
 
 // ---------------------------------------------------------------- ray queries
-// One launch of the query kernel (rt_query.hip) on `st`: a link of the scene's
-// chain like the guide launch -- it reads the tables the edits write, so it
-// runs after whatever was queued before it, and destroy waits for it.
-static int trace_check(const rt_scene *s, int64_t n, const void *rays, const void *hits) {
+// The query family: closest hits, occlusion and radiance differ in their kernel, their
+// output element and radiance's parameters; the rest is stated once (templates: outside the C block).
+} // extern "C"
+
+namespace {
+
+// The count and the arrays, the scene last: every other refusal needs no scene.
+int query_check(const rt_scene *s, int64_t n, const void *rays, const void *out, int64_t max_rays,
+                const char *too_many, const char *null_array) {
   if (n < 0) return set_err(RT_ERR_INVALID, "negative ray count");
-  if (n > ((int64_t)1 << 36)) return set_err(RT_ERR_INVALID, "more than 2^36 rays in one call");
-  if (n > 0 && (!rays || !hits)) return set_err(RT_ERR_INVALID, "null ray or hit array");
+  if (n > max_rays) return set_err(RT_ERR_INVALID, too_many);
+  if (n > 0 && (!rays || !out)) return set_err(RT_ERR_INVALID, null_array);
   if (!s) return set_err(RT_ERR_INVALID, "null scene");
   return RT_OK;
 }
-static int trace_on_stream(rt_scene *s, int64_t n, const rt_ray *d_rays, rt_ray_hit *d_hits, hipStream_t st) {
+int trace_check(const rt_scene *s, int64_t n, const void *rays, const void *out) {
+  return query_check(s, n, rays, out, (int64_t)1 << 36, "more than 2^36 rays in one call", "null ray or hit array");
+}
+struct QueryName { // what the errors of a query kind call its kernel and its call
+  const char *kernel, *call;
+};
+constexpr QueryName kTrace{"query", "query"}, kOcclusion{"occlusion", "occlusion query"},
+    kRadiance{"radiance", "radiance query"};
+std::string text(const char *a, const char *b) { return std::string(a) + b; }
+// One launch of a query kernel on `st`: a link of the scene's chain like the
+// guide launch -- it reads the tables the edits write, so it runs after
+// whatever was queued before it, and destroy waits for it.
+template <class Launch>
+int query_on_stream(rt_scene *s, hipStream_t st, const QueryName &what, const void *d_rays, void *d_out,
+                    Launch launch) {
+  DeviceGuard g(s->device);
   int rc = order_after_last(s, st);
   if (rc) return rc;
-  hipError_t e = rtk_launch_trace(&s->ds, s->xf_obj, n, d_rays, d_hits, st);
-  if (e != hipSuccess) return hip_err(e, "query kernel launch");
+  hipError_t e = launch((const rt_ray *)d_rays, d_out, st);
+  if (e != hipSuccess) return hip_err(e, text(what.kernel, " kernel launch").c_str());
   return mark_last(s, st);
 }
+// The host variants: n rays up, the launch on the scene's stream, out_bytes of
+// results down (and up first when `preload`: radiance's accumulate).  Only
+// this function uses trace_buf, on the scene's stream, and it synchronises
+// before it returns: the buffer is idle on entry, so it grows without a wait.
+template <class Launch>
+int query_from_host(rt_scene *s, int64_t n, const rt_ray *rays, void *out, size_t out_bytes, bool preload,
+                    const QueryName &what, Launch launch) {
+  DeviceGuard g(s->device);
+  const size_t ray_bytes = sizeof(rt_ray) * (size_t)n;
+  int rc = grow(s, s->trace_buf, s->trace_bytes, align256(ray_bytes) + out_bytes, Idle::Already,
+                text("hipMallocFromPoolAsync ", what.call).c_str());
+  if (rc) return rc;
+  void *d_out = s->trace_buf + align256(ray_bytes);
+  hipError_t e = hipMemcpyAsync(s->trace_buf, rays, ray_bytes, hipMemcpyHostToDevice, s->stream);
+  if (e == hipSuccess && preload) e = hipMemcpyAsync(d_out, out, out_bytes, hipMemcpyHostToDevice, s->stream);
+  if (e == hipSuccess) {
+    rc = query_on_stream(s, s->stream, what, s->trace_buf, d_out, launch);
+    if (rc == RT_OK) e = hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, s->stream);
+  }
+  const hipError_t es = hipStreamSynchronize(s->stream);
+  if (rc) return rc;
+  if (e != hipSuccess) return hip_err(e, text(what.call, " copy").c_str());
+  return es == hipSuccess ? RT_OK : hip_err(es, text(what.kernel, " kernel").c_str());
+}
+
+// The three launches: (device rays, device results, stream) -> hipError_t.
+auto trace_launch(rt_scene *s, int64_t n) {
+  return [s, n](const rt_ray *d_rays, void *d_hits, hipStream_t st) {
+    return rtk_launch_trace(&s->ds, s->xf_obj, n, d_rays, (rt_ray_hit *)d_hits, st);
+  };
+}
+auto occluded_launch(rt_scene *s, int64_t n) {
+  return [s, n](const rt_ray *d_rays, void *d_occ, hipStream_t st) {
+    return rtk_launch_occluded(&s->ds, n, d_rays, (uint8_t *)d_occ, st);
+  };
+}
+
+// The parameters first, then the family's checks with radiance's ray limit.
+int radiance_check(const rt_scene *s, int64_t n, const void *rays, const rt_radiance_params *p, const void *rgb) {
+  if (!p) return set_err(RT_ERR_INVALID, "null radiance params");
+  if (p->_reserved != 0) return set_err(RT_ERR_INVALID, "rt_radiance_params._reserved must be 0");
+  if (p->samples < 0) return set_err(RT_ERR_INVALID, "negative sample count");
+  if (p->first_sample < 0) return set_err(RT_ERR_INVALID, "negative first_sample");
+  if ((int64_t)p->first_sample + p->samples > 0x7fffffffll)
+    return set_err(RT_ERR_INVALID, "first_sample + samples overflows int32");
+  return query_check(s, n, rays, rgb, (int64_t)1 << 32, "more than 2^32 rays in one call: their keys would repeat",
+                     "null ray or rgb array");
+}
+// nothing to queue: no ray, or nothing to add onto what the buffer holds
+bool radiance_empty(int64_t n, const rt_radiance_params *p) {
+  return n == 0 || (p->samples == 0 && p->accumulate);
+}
+auto radiance_launch(rt_scene *s, int64_t n, const rt_radiance_params *p) {
+  return [s, n, p, C = rtr::radiance_camera(*p)](const rt_ray *d_rays, void *d_rgb, hipStream_t st) {
+    return rtk_launch_radiance(&s->ds, &C, p, n, d_rays, (double *)d_rgb, st);
+  };
+}
+
+} // namespace
+
+extern "C" {
 
 int rt_trace_device(rt_scene *s, int64_t n, const rt_ray *device_rays, rt_ray_hit *device_hits, void *hip_stream) {
   int rc = trace_check(s, n, device_rays, device_hits);
   if (rc || n == 0) return rc;
-  DeviceGuard g(s->device);
-  return trace_on_stream(s, n, device_rays, device_hits, (hipStream_t)hip_stream);
+  return query_on_stream(s, (hipStream_t)hip_stream, kTrace, device_rays, device_hits, trace_launch(s, n));
 }
 
 int rt_trace(rt_scene *s, int64_t n, const rt_ray *rays, rt_ray_hit *hits) {
   int rc = trace_check(s, n, rays, hits);
   if (rc || n == 0) return rc;
-  DeviceGuard g(s->device);
-  const size_t ray_bytes = sizeof(rt_ray) * (size_t)n, hit_bytes = sizeof(rt_ray_hit) * (size_t)n;
-  // only this function, rt_occluded and rt_radiance use trace_buf, on the scene's stream, and each synchronises
-  // before it returns
-  if ((rc = grow(s, s->trace_buf, s->trace_bytes, align256(ray_bytes) + hit_bytes, Idle::Already,
-                 "hipMallocFromPoolAsync query")))
-    return rc;
-  const rt_ray *d_rays = (const rt_ray *)s->trace_buf;
-  rt_ray_hit *d_hits = (rt_ray_hit *)(s->trace_buf + align256(ray_bytes));
-  hipError_t e = hipMemcpyAsync(s->trace_buf, rays, ray_bytes, hipMemcpyHostToDevice, s->stream);
-  if (e == hipSuccess) {
-    rc = trace_on_stream(s, n, d_rays, d_hits, s->stream);
-    if (rc == RT_OK) e = hipMemcpyAsync(hits, d_hits, hit_bytes, hipMemcpyDeviceToHost, s->stream);
-  }
-  const hipError_t es = hipStreamSynchronize(s->stream);
-  if (rc) return rc;
-  if (e != hipSuccess) return hip_err(e, "query copy");
-  return es == hipSuccess ? RT_OK : hip_err(es, "query kernel");
+  return query_from_host(s, n, rays, hits, sizeof(rt_ray_hit) * (size_t)n, false, kTrace, trace_launch(s, n));
 }
 
 int rt_pixel_ray(const rt_frame *f, double x, double y, rt_ray *ray) {
@@ -1171,45 +1238,18 @@ int rt_pixel_ray(const rt_frame *f, double x, double y, rt_ray *ray) {
 }
 
 // ---------------------------------------------------------- occlusion queries
-// One launch of the occlusion kernel (rt_occlusion.hip) on `st`: a link of the
-// scene's chain exactly as trace_on_stream is.
-static int occluded_on_stream(rt_scene *s, int64_t n, const rt_ray *d_rays, uint8_t *d_occ, hipStream_t st) {
-  int rc = order_after_last(s, st);
-  if (rc) return rc;
-  hipError_t e = rtk_launch_occluded(&s->ds, n, d_rays, d_occ, st);
-  if (e != hipSuccess) return hip_err(e, "occlusion kernel launch");
-  return mark_last(s, st);
-}
-
 int rt_occluded_device(rt_scene *s, int64_t n, const rt_ray *device_rays, uint8_t *device_occluded,
                        void *hip_stream) {
   int rc = trace_check(s, n, device_rays, device_occluded);
   if (rc || n == 0) return rc;
-  DeviceGuard g(s->device);
-  return occluded_on_stream(s, n, device_rays, device_occluded, (hipStream_t)hip_stream);
+  return query_on_stream(s, (hipStream_t)hip_stream, kOcclusion, device_rays, device_occluded,
+                         occluded_launch(s, n));
 }
 
 int rt_occluded(rt_scene *s, int64_t n, const rt_ray *rays, uint8_t *occluded) {
   int rc = trace_check(s, n, rays, occluded);
   if (rc || n == 0) return rc;
-  DeviceGuard g(s->device);
-  const size_t ray_bytes = sizeof(rt_ray) * (size_t)n, occ_bytes = (size_t)n;
-  // trace_buf is rt_trace's and this function's: both use it on the scene's
-  // stream and synchronise before they return
-  if ((rc = grow(s, s->trace_buf, s->trace_bytes, align256(ray_bytes) + occ_bytes, Idle::Already,
-                 "hipMallocFromPoolAsync occlusion query")))
-    return rc;
-  const rt_ray *d_rays = (const rt_ray *)s->trace_buf;
-  uint8_t *d_occ = (uint8_t *)(s->trace_buf + align256(ray_bytes));
-  hipError_t e = hipMemcpyAsync(s->trace_buf, rays, ray_bytes, hipMemcpyHostToDevice, s->stream);
-  if (e == hipSuccess) {
-    rc = occluded_on_stream(s, n, d_rays, d_occ, s->stream);
-    if (rc == RT_OK) e = hipMemcpyAsync(occluded, d_occ, occ_bytes, hipMemcpyDeviceToHost, s->stream);
-  }
-  const hipError_t es = hipStreamSynchronize(s->stream);
-  if (rc) return rc;
-  if (e != hipSuccess) return hip_err(e, "occlusion query copy");
-  return es == hipSuccess ? RT_OK : hip_err(es, "occlusion kernel");
+  return query_from_host(s, n, rays, occluded, (size_t)n, false, kOcclusion, occluded_launch(s, n));
 }
 
 int rt_segment_ray(const double a[3], const double b[3], double time, rt_ray *ray) {
@@ -1224,70 +1264,18 @@ int rt_segment_ray(const double a[3], const double b[3], double time, rt_ray *ra
 }
 
 // ----------------------------------------------------------- radiance queries
-// One launch of the radiance kernel (rt_radiance.hip) on `st`: a link of the
-// scene's chain exactly as trace_on_stream is.  The scene comes last in the
-// checks, as in trace_check: every other refusal needs no scene.
-static int radiance_check(const rt_scene *s, int64_t n, const void *rays, const rt_radiance_params *p,
-                          const void *rgb) {
-  if (!p) return set_err(RT_ERR_INVALID, "null radiance params");
-  if (p->_reserved != 0) return set_err(RT_ERR_INVALID, "rt_radiance_params._reserved must be 0");
-  if (p->samples < 0) return set_err(RT_ERR_INVALID, "negative sample count");
-  if (p->first_sample < 0) return set_err(RT_ERR_INVALID, "negative first_sample");
-  if ((int64_t)p->first_sample + p->samples > 0x7fffffffll)
-    return set_err(RT_ERR_INVALID, "first_sample + samples overflows int32");
-  if (n < 0) return set_err(RT_ERR_INVALID, "negative ray count");
-  if (n > ((int64_t)1 << 32))
-    return set_err(RT_ERR_INVALID, "more than 2^32 rays in one call: their keys would repeat");
-  if (n > 0 && (!rays || !rgb)) return set_err(RT_ERR_INVALID, "null ray or rgb array");
-  if (!s) return set_err(RT_ERR_INVALID, "null scene");
-  return RT_OK;
-}
-// nothing to queue: no ray, or nothing to add onto what the buffer holds
-static bool radiance_empty(int64_t n, const rt_radiance_params *p) {
-  return n == 0 || (p->samples == 0 && p->accumulate);
-}
-static int radiance_on_stream(rt_scene *s, int64_t n, const rt_ray *d_rays, const rt_radiance_params *p,
-                              double *d_rgb, hipStream_t st) {
-  DCamera C{}; // what segment and advance read of it: the background and the depth budget
-  C.bg[0] = p->background.x, C.bg[1] = p->background.y, C.bg[2] = p->background.z;
-  C.max_depth = p->max_depth;
-  int rc = order_after_last(s, st);
-  if (rc) return rc;
-  hipError_t e = rtk_launch_radiance(&s->ds, &C, p, n, d_rays, d_rgb, st);
-  if (e != hipSuccess) return hip_err(e, "radiance kernel launch");
-  return mark_last(s, st);
-}
-
 int rt_radiance_device(rt_scene *s, int64_t n, const rt_ray *device_rays, const rt_radiance_params *p,
                        double *device_rgb, void *hip_stream) {
   int rc = radiance_check(s, n, device_rays, p, device_rgb);
   if (rc || radiance_empty(n, p)) return rc;
-  DeviceGuard g(s->device);
-  return radiance_on_stream(s, n, device_rays, p, device_rgb, (hipStream_t)hip_stream);
+  return query_on_stream(s, (hipStream_t)hip_stream, kRadiance, device_rays, device_rgb, radiance_launch(s, n, p));
 }
 
 int rt_radiance(rt_scene *s, int64_t n, const rt_ray *rays, const rt_radiance_params *p, double *rgb) {
   int rc = radiance_check(s, n, rays, p, rgb);
   if (rc || radiance_empty(n, p)) return rc;
-  DeviceGuard g(s->device);
-  const size_t ray_bytes = sizeof(rt_ray) * (size_t)n, rgb_bytes = 3 * sizeof(double) * (size_t)n;
-  // trace_buf is rt_trace's, rt_occluded's and this function's: each uses it on
-  // the scene's stream and synchronises before it returns
-  if ((rc = grow(s, s->trace_buf, s->trace_bytes, align256(ray_bytes) + rgb_bytes, Idle::Already,
-                 "hipMallocFromPoolAsync radiance query")))
-    return rc;
-  const rt_ray *d_rays = (const rt_ray *)s->trace_buf;
-  double *d_rgb = (double *)(s->trace_buf + align256(ray_bytes));
-  hipError_t e = hipMemcpyAsync(s->trace_buf, rays, ray_bytes, hipMemcpyHostToDevice, s->stream);
-  if (e == hipSuccess && p->accumulate) e = hipMemcpyAsync(d_rgb, rgb, rgb_bytes, hipMemcpyHostToDevice, s->stream);
-  if (e == hipSuccess) {
-    rc = radiance_on_stream(s, n, d_rays, p, d_rgb, s->stream);
-    if (rc == RT_OK) e = hipMemcpyAsync(rgb, d_rgb, rgb_bytes, hipMemcpyDeviceToHost, s->stream);
-  }
-  const hipError_t es = hipStreamSynchronize(s->stream);
-  if (rc) return rc;
-  if (e != hipSuccess) return hip_err(e, "radiance query copy");
-  return es == hipSuccess ? RT_OK : hip_err(es, "radiance kernel");
+  return query_from_host(s, n, rays, rgb, 3 * sizeof(double) * (size_t)n, p->accumulate != 0, kRadiance,
+                         radiance_launch(s, n, p));
 }
 
 int rt_camera_rays(const rt_frame *f, uint64_t seed, int32_t stratum, int32_t row_begin, int32_t row_end,

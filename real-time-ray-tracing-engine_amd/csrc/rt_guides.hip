@@ -13,13 +13,11 @@
 // a guide sample never shades).  Nothing is staged: the walks read nodes and
 // the Perlin table from memory (rt_guides.h guide_scene), the dynamic LDS is
 // the traversal stacks [block_waves(F)][stack_depth][64] alone.
+// Lane set-up and launch: rt_ray_launch.h; the instance table: rt_path.h feature_table.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <math.h>
-
-#include <array>
-#include <utility>
 
 #include "rt_kernels.h"
 #include "rt_lds_plan.h"
@@ -30,6 +28,7 @@
 #pragma clang attribute push(__attribute__((internal_linkage)), apply_to = function)
 #include "rt_guides.h"
 #pragma clang attribute pop
+#include "rt_ray_launch.h"
 
 namespace {
 
@@ -37,13 +36,12 @@ using namespace rtg;
 
 template <unsigned F>
 __global__ __launch_bounds__(64 * block_waves(F)) void guides_kernel(DScene S_, DCamera C, DLaunch P, double *out) {
-  constexpr int BW = block_waves(F);
   extern __shared__ int4 dyn_lds[];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int tile = blockIdx.x * BW + wv;
+  const rtl::RayLane L;
+  const int lane = L.lane, tile = L.wave<block_waves(F)>();
   if (tile >= P.tiles_x * P.tiles_y) return; // wave-uniform; no block-wide barrier below
   const DScene S = guide_scene(S_);
-  int *stk = reinterpret_cast<int *>(dyn_lds) + wv * S.stack_depth * 64 + lane;
+  int *stk = rtl::lane_stack(L, dyn_lds, S.stack_depth);
   const int i = (tile % P.tiles_x) * 8 + (lane & 7);
   const int j = P.row_begin + (tile / P.tiles_x) * 8 + (lane >> 3);
   if (i >= C.W || j >= P.row_end) return; // pixels outside the image are not written
@@ -51,29 +49,17 @@ __global__ __launch_bounds__(64 * block_waves(F)) void guides_kernel(DScene S_, 
   guide_pixel<F>(S, C, P.seed_lo, P.seed_hi, i, j, P.sample_begin, P.sample_count, P.accumulate, stk, px);
 }
 
-using GuideFn = void (*)(DScene, DCamera, DLaunch, double *);
-
-// one instance per feature set without F_LIGHTS; F_BVH4 never comes with
-// F_FLAT (rt_kernel.hip canonical)
-constexpr unsigned canonical(unsigned f) {
-  return guide_features((f & F_FLAT) ? (f & ~(unsigned)F_BVH4) : f);
-}
-template <unsigned... Fs>
-constexpr std::array<GuideFn, sizeof...(Fs)> instance_table(std::integer_sequence<unsigned, Fs...>) {
-  return {guides_kernel<canonical(Fs)>...};
-}
+// one instance per feature set without F_LIGHTS
+constexpr unsigned guide_instance(unsigned f) { return guide_features(canonical_features(f)); }
 
 } // namespace
 
 extern "C" hipError_t rtk_launch_guides(const DScene *S, const DCamera *C, const DLaunch *P, double *out,
                                         hipStream_t stream) {
-  static constexpr auto table = instance_table(std::make_integer_sequence<unsigned, F_ALL + 1>{});
+  static constexpr auto table = feature_table([](auto f) { return guides_kernel<guide_instance(decltype(f)::value)>; });
   const unsigned f = (unsigned)(S->features & F_ALL);
-  const int bw = block_waves(canonical(f));
-  const int64_t tiles = (int64_t)P->tiles_x * P->tiles_y;
-  if (tiles <= 0 || P->sample_count < 0) return hipSuccess;
-  const size_t lds = lds_bytes((int)canonical(f), S->stack_depth, 0);
-  hipLaunchKernelGGL(table[f], dim3((unsigned)((tiles + bw - 1) / bw)), dim3(64 * bw), lds, stream, *S, *C, *P,
-                     out);
-  return hipGetLastError();
+  if (P->sample_count < 0) return hipSuccess;
+  // a wave's tile is its 64 rays
+  return rtl::launch_per_ray(table[f], guide_instance(f), S->stack_depth, (int64_t)P->tiles_x * P->tiles_y * 64, stream,
+                             *S, *C, *P, out);
 }

@@ -635,12 +635,10 @@ __global__ __launch_bounds__(64 * (PCW ? PCW : block_waves(F))) __attribute__((a
 
 using RenderFn = void (*)(DScene, DCamera, DLaunch, double *, unsigned long long *);
 
-// F_BVH4 never comes with F_FLAT (a flat world has no tree): those slots reuse
-// the flat instance instead of instantiating a kernel that cannot be launched
-constexpr unsigned canonical(unsigned f) { return (f & F_FLAT) ? (f & ~F_BVH4) : f; }
+// the F_FLAT | F_BVH4 slots reuse the flat instance (rt_path.h canonical_features)
 template <bool STATS, unsigned... Fs>
 constexpr std::array<RenderFn, sizeof...(Fs)> instance_table(std::integer_sequence<unsigned, Fs...>) {
-  return {render_tiles<STATS, canonical(Fs)>...};
+  return {render_tiles<STATS, canonical_features(Fs)>...};
 }
 
 // the persistent instances (RT_PERSIST_F feature sets), blocks of pcw waves

@@ -13,13 +13,11 @@
 // F_XFORM, F_FLAT, F_BVH4).  Nothing is staged: the walks read nodes from
 // memory (query_scene), the dynamic LDS is the traversal stacks
 // [block_waves(F)][stack_depth][64] alone.
+// Lane set-up and launch: rt_ray_launch.h; the instance table: rt_path.h feature_table.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <math.h>
-
-#include <array>
-#include <utility>
 
 #include "rt_kernels.h"
 #include "rt_lds_plan.h"
@@ -28,6 +26,7 @@
 #pragma clang attribute push(__attribute__((internal_linkage)), apply_to = function)
 #include "rt_occlusion.h"
 #pragma clang attribute pop
+#include "rt_ray_launch.h"
 
 namespace {
 
@@ -36,35 +35,22 @@ using namespace rto;
 template <unsigned F>
 __global__ __launch_bounds__(64 * block_waves(F)) void occlusion_kernel(DScene S_, int64_t n, const rt_ray *rays,
                                                                         uint8_t *occluded) {
-  constexpr int BW = block_waves(F);
   extern __shared__ int4 dyn_lds[];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int64_t k = ((int64_t)blockIdx.x * BW + wv) * 64 + lane;
-  if (k >= n) return; // rays past n are neither traced nor written; no block-wide barrier below
+  const rtl::RayLane L;
+  const int64_t k = L.ray<block_waves(F)>();
+  if (k >= n) return; // rays past n are neither traced nor written
   const DScene S = query_scene(S_);
-  int *stk = reinterpret_cast<int *>(dyn_lds) + wv * S.stack_depth * 64 + lane;
+  int *stk = rtl::lane_stack(L, dyn_lds, S.stack_depth);
   const rt_ray q = rays[k];
   occluded[k] = occluded_ray<F>(S, q, stk);
-}
-
-using OcclusionFn = void (*)(DScene, int64_t, const rt_ray *, uint8_t *);
-
-template <unsigned... Fs>
-constexpr std::array<OcclusionFn, sizeof...(Fs)> instance_table(std::integer_sequence<unsigned, Fs...>) {
-  return {occlusion_kernel<query_features(Fs)>...};
 }
 
 } // namespace
 
 extern "C" hipError_t rtk_launch_occluded(const DScene *S, int64_t n, const rt_ray *rays, uint8_t *occluded,
                                           hipStream_t stream) {
-  static constexpr auto table = instance_table(std::make_integer_sequence<unsigned, F_ALL + 1>{});
-  if (n <= 0) return hipSuccess;
+  static constexpr auto table =
+      feature_table([](auto f) { return occlusion_kernel<query_features(decltype(f)::value)>; });
   const unsigned f = (unsigned)(S->features & F_ALL);
-  const int per_block = 64 * block_waves(query_features(f));
-  const int64_t blocks = (n + per_block - 1) / per_block;
-  if (blocks > 0x7fffffffll) return hipErrorInvalidValue;
-  const size_t lds = lds_bytes((int)query_features(f), S->stack_depth, 0);
-  hipLaunchKernelGGL(table[f], dim3((unsigned)blocks), dim3(per_block), lds, stream, *S, n, rays, occluded);
-  return hipGetLastError();
+  return rtl::launch_per_ray(table[f], query_features(f), S->stack_depth, n, stream, *S, n, rays, occluded);
 }

@@ -11,6 +11,9 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <array>
+#include <utility>
+
 #include "../../include/rt_api.h"
 #include "rt_layout.h"
 
@@ -383,6 +386,20 @@ enum : unsigned {
   F_BVH4 = 32u,  // 4-wide world BVH (DNode4); never with F_FLAT
   F_ALL = 63u
 };
+// The feature set whose instance serves `f`: F_BVH4 never comes with F_FLAT (a flat world has no
+// tree), so those slots of an instance table reuse the flat instance.
+constexpr unsigned canonical_features(unsigned f) { return (f & F_FLAT) ? (f & ~(unsigned)F_BVH4) : f; }
+// One entry per feature set [0, N): pick(std::integral_constant<unsigned, f>) names the instance -- a
+// kernel, or a host function of the same source -- that serves f.
+template <class Pick, unsigned... Fs>
+constexpr auto feature_table(Pick pick, std::integer_sequence<unsigned, Fs...>) {
+  using Fn = decltype(pick(std::integral_constant<unsigned, 0u>{}));
+  return std::array<Fn, sizeof...(Fs)>{pick(std::integral_constant<unsigned, Fs>{})...};
+}
+template <unsigned N = F_ALL + 1, class Pick>
+constexpr auto feature_table(Pick pick) {
+  return feature_table(pick, std::make_integer_sequence<unsigned, N>{});
+}
 // The material set an instance is compiled for (shade, tex_value): a key beside
 // the feature set, from the scene's materials table (rt_scene.h diffuse_only,
 // RT_FEAT_DIFFUSE).  M_DIFFUSE: every material is Lambertian with a solid

@@ -36,6 +36,15 @@ RT_HD RT_FI DRadiance radiance_launch(const rt_radiance_params &p, int64_t n) {
                    p.samples, p.accumulate};
 }
 
+// The DCamera of a radiance call: what segment and advance read of one, the
+// background and the depth budget (the library and the host twin alike).
+RT_HD RT_FI DCamera radiance_camera(const rt_radiance_params &p) {
+  DCamera C{};
+  C.bg[0] = p.background.x, C.bg[1] = p.background.y, C.bg[2] = p.background.z;
+  C.max_depth = p.max_depth;
+  return C;
+}
+
 // The material set of a scene's instance: render_instance's rule (rt_kernel.hip)
 // -- the Lambertian-only twin for the plain flat world of a diffuse-only table.
 RT_HD RT_FI bool diffuse_twin(int features) {

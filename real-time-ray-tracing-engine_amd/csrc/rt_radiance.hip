@@ -18,13 +18,11 @@
 // the Perlin table from memory (radiance_scene), the dynamic LDS is the
 // traversal stacks [block_waves(F)][stack_depth][64] alone.  No persistent
 // units, no work-unit plan, no cost order, none of the scene's scratch.
+// Lane set-up and launch: rt_ray_launch.h; the instance table: rt_path.h feature_table.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <math.h>
-
-#include <array>
-#include <utility>
 
 #include "rt_kernels.h"
 #include "rt_lds_plan.h"
@@ -33,6 +31,7 @@
 #pragma clang attribute push(__attribute__((internal_linkage)), apply_to = function)
 #include "rt_radiance.h"
 #pragma clang attribute pop
+#include "rt_ray_launch.h"
 
 namespace {
 
@@ -46,13 +45,12 @@ using namespace rtr;
 template <unsigned F, MatSet MS>
 __global__ __launch_bounds__(64 * block_waves(F)) __attribute__((amdgpu_waves_per_eu(RT_RADIANCE_WAVES_PER_EU(F)))) void
 radiance_kernel(DScene S_, DCamera C, DRadiance P, const rt_ray *rays, double *rgb) {
-  constexpr int BW = block_waves(F);
   extern __shared__ int4 dyn_lds[];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int64_t k = ((int64_t)blockIdx.x * BW + wv) * 64 + lane;
-  if (k >= P.n) return; // rays past n are neither traced nor written; no block-wide barrier below
+  const rtl::RayLane L;
+  const int64_t k = L.ray<block_waves(F)>();
+  if (k >= P.n) return; // rays past n are neither traced nor written
   const DScene S = radiance_scene(S_);
-  int *stk = reinterpret_cast<int *>(dyn_lds) + wv * S.stack_depth * 64 + lane;
+  int *stk = rtl::lane_stack(L, dyn_lds, S.stack_depth);
   const rt_ray *q = rays + k;
   double *px = rgb + 3 * k;
   RadianceState st = radiance_begin(C, P, k, *q, px);
@@ -69,17 +67,11 @@ radiance_kernel(DScene S_, DCamera C, DRadiance P, const rt_ray *rays, double *r
 
 using RadianceFn = void (*)(DScene, DCamera, DRadiance, const rt_ray *, double *);
 
-// F_BVH4 never comes with F_FLAT (rt_kernel.hip canonical)
-constexpr unsigned canonical(unsigned f) { return (f & F_FLAT) ? (f & ~(unsigned)F_BVH4) : f; }
-template <unsigned... Fs>
-constexpr std::array<RadianceFn, sizeof...(Fs)> instance_table(std::integer_sequence<unsigned, Fs...>) {
-  return {radiance_kernel<canonical(Fs), M_ANY>...};
-}
-
 // render_instance's choice (rt_kernel.hip): the table's instance, or the
 // Lambertian-only twin of the plain flat world
 RadianceFn radiance_instance(int features) {
-  static constexpr auto table = instance_table(std::make_integer_sequence<unsigned, F_ALL + 1>{});
+  static constexpr auto table =
+      feature_table([](auto f) { return radiance_kernel<canonical_features(decltype(f)::value), M_ANY>; });
   if (diffuse_twin(features)) return radiance_kernel<F_FLAT, M_DIFFUSE>;
   return table[features & F_ALL];
 }
@@ -88,15 +80,8 @@ RadianceFn radiance_instance(int features) {
 
 extern "C" hipError_t rtk_launch_radiance(const DScene *S, const DCamera *C, const rt_radiance_params *p, int64_t n,
                                           const rt_ray *rays, double *rgb, hipStream_t stream) {
-  if (n <= 0) return hipSuccess;
-  const unsigned f = canonical((unsigned)(S->features & F_ALL));
-  const int per_block = 64 * block_waves(f);
-  const int64_t blocks = (n + per_block - 1) / per_block;
-  if (blocks > 0x7fffffffll) return hipErrorInvalidValue;
-  const size_t lds = lds_bytes((int)f, S->stack_depth, 0);
-  hipLaunchKernelGGL(radiance_instance(S->features), dim3((unsigned)blocks), dim3(per_block), lds, stream, *S, *C,
-                     radiance_launch(*p, n), rays, rgb);
-  return hipGetLastError();
+  return rtl::launch_per_ray(radiance_instance(S->features), canonical_features((unsigned)(S->features & F_ALL)),
+                             S->stack_depth, n, stream, *S, *C, radiance_launch(*p, n), rays, rgb);
 }
 
 // The render's camera rays on the host (rt_camera_rays): camera_ray of

@@ -1,4 +1,5 @@
-// rt_scene.h — host scene compiler: rt_scene_desc -> flat device layout.
+// rt_scene.h — host scene compiler: rt_scene_desc -> flat device layout, and
+// the host binding of a compiled scene (BoundHostScene).
 #ifndef RT_SCENE_H
 #define RT_SCENE_H
 #include "../../include/rt_api.h"
@@ -170,10 +171,9 @@ inline void bind_counts(DScene &S, const HostScene &H) {
   S.features = scene_features(H) | (H.root_is_leaf ? RT_FEAT_FLAT : 0) | (diffuse_only(H) ? RT_FEAT_DIFFUSE : 0);
 }
 
-// The host binder: a DScene over the HostScene's own vectors (the CPU
-// backend, host/rtx_cpu.cpp; the kernel-source emulator, tests/native/
-// rt_emulate.cpp, which then points `nodes` at the 4-wide collapse).  The LDS
-// fields stay 0; stack_depth is the caller's (traversal_stack_depth).
+// A DScene over the HostScene's own vectors, the binary tree in `nodes`.  The
+// LDS fields stay 0; stack_depth is the caller's (traversal_stack_depth).
+// BoundHostScene below is the whole host binding, 4-wide tree included.
 inline DScene bind_host_scene(const HostScene &H) {
   DScene S{};
   for_each_table([&](auto dm, auto hm) { S.*dm = (H.*hm).data(); });
@@ -191,6 +191,11 @@ void build_world_bvh_host(HostScene &H);
 // Scenes with at least this many world primitives walk a 4-wide BVH when
 // rt_scene_desc.bvh_arity is 0 (auto).
 constexpr int kBvh4Min = 4096;
+// The arity rule: whether a description's world walks a 4-wide tree, where it
+// has a tree at all (rt_scene_create*; the kernels' host twins).
+inline bool wants_bvh4(const rt_scene_desc *desc, const HostScene &H) {
+  return desc->bvh_arity == 4 || (desc->bvh_arity == 0 && H.items.size() >= (size_t)kBvh4Min);
+}
 
 // Collapses the binary BFS-ordered tree `bin` (root 0) into 4-wide nodes, BFS
 // order, root 0: each 4-wide node starts from one binary node's two children
@@ -242,6 +247,40 @@ int camera_setup(const rt_camera_desc *cam, rt_frame *frame, std::string &err);
 // RT_CHUNKS_AUTO is resolved by the callers that accept it.
 int device_camera(const rt_frame *frame, DCamera &c, std::string &err);
 int launch_geometry(const rt_frame *frame, const rt_render_params *p, DLaunch &L, std::string &err);
+
+// A description as host code walks it (the CPU backend, host/rtx_cpu.cpp; the kernels' host twins,
+// tests/native/*_emu.cpp, rt_emulate.cpp): compiled, its world tree built by the host builder whatever
+// builder it names (the device builders need a GPU), collapsed to 4-wide nodes when wanted and there is
+// a tree -- S.nodes / n_nodes are then that tree and S.features has RT_FEAT_BVH4, as in the GPU library's
+// DScene -- and S.stack_depth the tree's.  Owns the HostScene that S points into.  bind: RT_OK,
+// compile_scene's code (compiled false) or RT_ERR_UNSUPPORTED for a tree deeper than the stack, `err` filled.
+struct BoundHostScene {
+  HostScene H; // the sah_* overrides may be set before bind
+  DScene S{};
+  std::string err;
+  bool compiled = false;
+  BoundHostScene() = default;
+  BoundHostScene(const BoundHostScene &) = delete; // S points into H
+  bool bvh4() const { return H.bvh_arity == 4; }
+  // want4: 1 / 0 the caller's choice of tree, -1 the library's (wants_bvh4)
+  int bind(const rt_scene_desc *desc, int want4 = -1) {
+    if (int rc = compile_scene(desc, H, err)) return rc;
+    compiled = true;
+    if (H.device_bvh) build_world_bvh_host(H);
+    if ((want4 < 0 ? wants_bvh4(desc, H) : want4 != 0) && !H.root_is_leaf && !H.nodes.empty()) {
+      H.bvh_depth4 = collapse_bvh4(H.nodes, H.nodes4);
+      H.bvh_arity = 4;
+    }
+    S = bind_host_scene(H);
+    if (bvh4()) {
+      S.nodes = (const DNode *)(const void *)H.nodes4.data();
+      S.n_nodes = (int32_t)H.nodes4.size();
+      S.features |= RT_FEAT_BVH4;
+    }
+    S.stack_depth = traversal_stack_depth(H, err);
+    return S.stack_depth ? RT_OK : RT_ERR_UNSUPPORTED;
+  }
+};
 
 } // namespace rtx
 #endif

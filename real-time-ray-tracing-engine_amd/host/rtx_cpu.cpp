@@ -113,13 +113,10 @@ int rt_cpu_render(const rt_scene_desc *desc, const rt_frame *f, const rt_render_
   if (rc != RT_OK) return fail(rc, err);
   if (L.accumulate) return fail(RT_ERR_INVALID, "rt_cpu_render writes its output (accumulate 0)");
 
-  rtx::HostScene H;
-  rc = rtx::compile_scene(desc, H, err);
-  if (rc != RT_OK) return fail(rc, err);
-  if (H.device_bvh) rtx::build_world_bvh_host(H); // the device builders are the GPU library's
-  DScene S = rtx::bind_host_scene(H);
-  S.stack_depth = rtx::traversal_stack_depth(H, err);
-  if (!S.stack_depth) return fail(RT_ERR_UNSUPPORTED, err);
+  rtx::BoundHostScene B; // the binary tree, built on the host: the device builders are the GPU library's
+  if ((rc = B.bind(desc, 0))) return fail(rc, B.err);
+  const rtx::HostScene &H = B.H;
+  DScene S = B.S;
   S.n_lds_nodes = S.n_nodes; // the walk reads every node from `lnodes`, in the staged form
   std::vector<DNodeL> lnodes_l;
   const DNode *lnodes = S.nodes;

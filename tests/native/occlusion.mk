@@ -4,6 +4,6 @@
 # renamed, as in Makefile: parallel test workers may run this at once)
 CXX ?= g++
 PKG := ../../real-time-ray-tracing-engine_amd
-build/libocclusion_emu.so: rt_occlusion_emu.cpp $(PKG)/csrc/rt_occlusion.h $(PKG)/csrc/rt_query.h $(PKG)/csrc/rt_path.h $(PKG)/csrc/rt_layout.h $(PKG)/csrc/rt_scene.cpp $(PKG)/csrc/rt_scene.h $(PKG)/csrc/rt_collapse.h $(PKG)/csrc/rt_plan.h ../../include/rt_api.h
+build/libocclusion_emu.so: rt_occlusion_emu.cpp query_worlds.h $(PKG)/csrc/rt_occlusion.h $(PKG)/csrc/rt_query.h $(PKG)/csrc/rt_path.h $(PKG)/csrc/rt_layout.h $(PKG)/csrc/rt_scene.cpp $(PKG)/csrc/rt_scene.h $(PKG)/csrc/rt_collapse.h $(PKG)/csrc/rt_plan.h ../../include/rt_api.h
 	@mkdir -p build
 	$(CXX) -std=c++17 -O2 -ffp-contract=off -fPIC -shared -w -o $@.$$$$ rt_occlusion_emu.cpp $(PKG)/csrc/rt_scene.cpp && mv -f $@.$$$$ $@

@@ -62,26 +62,15 @@ constexpr auto kFnsStats = pixel_fns<true>(std::make_integer_sequence<unsigned, 
 // counted instance; `out` may be null)
 int render_host(const rt_scene_desc *desc, const rt_frame *f, const rt_render_params *p,
                 int features, double *out, rt_path_stats *stats) {
-  rtx::HostScene H;
-  std::string err;
-  if (rtx::compile_scene(desc, H, err) != RT_OK) return -1;
-  if (H.device_bvh) rtx::build_world_bvh_host(H); // the device builder needs a GPU
   // features bit 5 (F_BVH4): walk the 4-wide collapse of the same tree, as the
-  // library does for large scenes (rt_api.cpp)
-  const bool bvh4 = (features & F_BVH4) && !H.root_is_leaf && !H.nodes.empty();
-  if (bvh4) {
-    H.bvh_depth4 = rtx::collapse_bvh4(H.nodes, H.nodes4);
-    H.bvh_arity = 4;
-  }
-  DScene S = rtx::bind_host_scene(H);
-  if (bvh4) {
-    S.nodes = (const DNode *)(const void *)H.nodes4.data();
-    S.n_nodes = (int32_t)H.nodes4.size();
-  }
-  S.features = features;
-  // rt_scene_create's rule: a tree deeper than the stack is refused, not clamped
-  S.stack_depth = rtx::traversal_stack_depth(H, err);
-  if (!S.stack_depth) return -2;
+  // library does for large scenes; rt_scene_create's rule: a tree deeper than
+  // the stack is refused, not clamped (rt_scene.h BoundHostScene)
+  rtx::BoundHostScene B;
+  if (B.bind(desc, (features & F_BVH4) != 0 ? 1 : 0)) return B.compiled ? -2 : -1;
+  const rtx::HostScene &H = B.H;
+  const bool bvh4 = B.bvh4();
+  DScene S = B.S;
+  S.features = features; // the caller's instance, not the scene's
   S.n_lds_nodes = S.n_nodes; // host: the whole tree is the "LDS" copy
   // in the form the kernel stages it: DNode4 as is, binary nodes as DNodeL
   std::vector<DNodeL> lnodes_l;

@@ -22,15 +22,9 @@ using namespace rtg;
 
 namespace {
 
-typedef void (*PixelFn)(const DScene &, const DCamera &, uint32_t, uint32_t, int, int, int, int, int, int *,
-                        double *);
-constexpr unsigned canonical(unsigned f) { return guide_features((f & F_FLAT) ? (f & ~(unsigned)F_BVH4) : f); }
-template <unsigned... Fs>
-constexpr std::array<PixelFn, sizeof...(Fs)> pixel_fns(std::integer_sequence<unsigned, Fs...>) {
-  return {guide_pixel<canonical(Fs)>...};
-}
-// one per guide instance (rt_guides.hip instance_table)
-constexpr auto kFns = pixel_fns(std::make_integer_sequence<unsigned, F_ALL + 1>{});
+// one per guide instance (rt_guides.hip)
+constexpr auto kFns =
+    feature_table([](auto f) { return &guide_pixel<guide_features(canonical_features(decltype(f)::value))>; });
 
 } // namespace
 
@@ -39,13 +33,10 @@ constexpr auto kFns = pixel_fns(std::make_integer_sequence<unsigned, F_ALL + 1>{
 // library picks for the scene.  features_out (may be null): that instance's bits.
 extern "C" int emu_guides(const rt_scene_desc *desc, const rt_frame *f, const rt_render_params *p, double *out,
                           int *features_out) {
-  rtx::HostScene H;
+  rtx::BoundHostScene B;
+  if (B.bind(desc, 0)) return B.compiled ? -2 : -1; // the binary tree: the first hit is the same on either
+  const DScene &S = B.S;
   std::string err;
-  if (rtx::compile_scene(desc, H, err) != RT_OK) return -1;
-  if (H.device_bvh) rtx::build_world_bvh_host(H); // the device builder needs a GPU
-  DScene S = rtx::bind_host_scene(H);
-  S.stack_depth = rtx::traversal_stack_depth(H, err);
-  if (!S.stack_depth) return -2;
   const DScene G = guide_scene(S); // nothing staged: the walks read S.nodes
   DCamera C;
   DLaunch L;
@@ -53,7 +44,7 @@ extern "C" int emu_guides(const rt_scene_desc *desc, const rt_frame *f, const rt
   if (rtx::launch_geometry(f, p, L, err) != RT_OK) return -4;
   if (features_out) *features_out = S.features;
   std::vector<int> stack((size_t)std::max(RT_STACK_DEPTH, RT_STACK_DEPTH4) * 64);
-  const PixelFn fn = kFns[S.features & F_ALL];
+  const auto fn = kFns[S.features & F_ALL];
   for (int j = L.row_begin; j < L.row_end; ++j)
     for (int i = 0; i < C.W; ++i)
       fn(G, C, L.seed_lo, L.seed_hi, i, j, L.sample_begin, L.sample_count, L.accumulate, stack.data(),
