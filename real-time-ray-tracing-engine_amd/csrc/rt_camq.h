@@ -38,6 +38,11 @@ constexpr int kEntries = kBatch * kBatches;
 // doubles of an entry: ray direction, ray time, ray origin (written and read
 // only with a defocus disk; without one the origin is the camera centre)
 constexpr int kComps = 7;
+// Without a defocus disk the batch is traced where it is generated, and the
+// first two origin components hold the outcome instead: the closest root, and
+// the world item it belongs to (an int in the double's low bits; -1: a miss).
+constexpr int kClosest = 4;
+constexpr int kBest = 5;
 
 // One past the last item the pop of a refill reads: idle lane of rank r takes
 // item next_item + r while that is an item of the unit.

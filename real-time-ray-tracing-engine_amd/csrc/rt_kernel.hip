@@ -388,6 +388,39 @@ __global__ __launch_bounds__(64 * (PCW ? PCW : block_waves(F))) __attribute__((a
   PathState ps;
   ps.active = false;
   Key key{P.seed_lo, P.seed_hi, 0, 0};
+  // gen_trace: camera-ray batches are traced where they are generated (the
+  // refill below) -- no defocus disk, a world with a root table, whose walk
+  // is the root tests alone (rt_path.h trace_closest_roots), and a unit of
+  // more than one batch: a one-batch unit (the progressive frames) is popped
+  // by all 64 lanes at once and traced at full lane use as it is, and measured
+  // 1.2-2.5 % slower with the detour (profiles/batch_progressive_ab.log).  A flat world
+  // without a table (a quad, a moving or a transformed sphere among its root
+  // items) keeps the flow of a camera with a disk: the whole walk inlined a
+  // second time costs the Lambertian-only instance its register advantage
+  // (127 VGPRs, the general instance's count, and 2 of them spilled).
+  // org_tab: every camera ray of the unit leaves the camera centre, so the
+  // (oc, c) per root (rt_path.h root_origin) are formed here once per unit
+  // and the generation-time trace reads them from LDS, one address in
+  // every lane; a table of more than kRootOriginMax roots takes the general
+  // root test there.  Both wave-uniform.
+  [[maybe_unused]] bool gen_trace = false, org_tab = false;
+  [[maybe_unused]] const RT_LDS RootOrigin *root_org = nullptr;
+  if constexpr (kCamq) {
+    __shared__ RootOrigin root_org_lds[kRootOriginMax > 0 ? kRootOriginMax : 1];
+    root_org = (const RT_LDS RootOrigin *)&root_org_lds[0];
+    gen_trace = RT_ROOT_TABLE_F(F) && n_items > rtq::kBatch && C.defocus_angle <= 0 && S.n_roots > 0;
+    org_tab = gen_trace && S.n_roots <= kRootOriginMax;
+    if (org_tab) { // a unit that does not read the table pays nothing for it
+      const DCamera Co = camera_fields<true>(C);
+      for (int ii = 0; ii < S.n_roots; ++ii) { // the walk's own scalar loads: no vector load opens a unit
+        const RootOrigin q = root_origin(ldu<true>(&S.roots[ii].test, 0), ld3(Co.center));
+        if (lane == 0) root_org_lds[ii] = q;
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+  }
   // a parked lane's hit (RT_PARK_MIN): pk_best >= 0 is the flag
   constexpr int kPark = RT_PARK_MIN(F);
   [[maybe_unused]] double pk_closest = 0.0;
@@ -408,8 +441,14 @@ __global__ __launch_bounds__(64 * (PCW ? PCW : block_waves(F))) __attribute__((a
         // the ray of pixel slot l in the batch's stratum (wave-uniform: the
         // stratum's cell and key.sample on the scalar side); then the idle
         // lanes pop their items.  A ray's arithmetic is camera_ray's, whichever
-        // lane runs it, and the lane that traces and shades an item is the one
-        // that did before: frames keep their bits.
+        // lane runs it.  Where gen_trace holds (above) the batch is traced right
+        // there, at full lane use and once per batch: a popped hit arrives
+        // parked, a popped miss adds the background and leaves its lane idle,
+        // and the refill loop's own repeat (RT_REGEN_MIN idle lanes, items
+        // left) fills such lanes again.  The path loop's trace site then sees
+        // bounce rays only.  Every ray, root and weight keeps its bits; what
+        // moves is when a sky sample joins its pixel's sum.  Otherwise nothing
+        // is traced here and a popped lane is traced by the path loop.
         static_assert(BW == 1, "the camera-ray queue is one wave's");
         __shared__ double camq[rtq::kComps][rtq::kEntries];
         const DCamera &Cr = C;
@@ -437,6 +476,30 @@ __global__ __launch_bounds__(64 * (PCW ? PCW : block_waves(F))) __attribute__((a
             camq[4][e] = gr.o.x;
             camq[5][e] = gr.o.y;
             camq[6][e] = gr.o.z;
+          } else if (gen_trace) {
+            // ---- traced at generation: the batch is complete here, so the
+            // closest-hit search of its camera rays runs with every lane of an
+            // inside tile, once per batch, and the entry carries its outcome
+            // in the origin's place (rtq::kClosest, rtq::kBest; best -1: a
+            // miss).  The search is the root-table walk of the path loop's
+            // own (trace_closest) on the ray the popping lane would have traced:
+            // (closest, best) keep their bits.  A slot outside the image and a depth-0 launch are
+            // not traced, as they never were; their entries are not read.
+            double g_closest = 0.0;
+            int g_best = -1;
+            if (gi < Cg.W && gj < P.row_end && Cg.max_depth > 0) {
+              if (STATS) n_segments++;
+              // timed into cyc_trace like every trace; it also lies inside cyc_regen's
+              // span, so the two phase shares overlap by this much
+              const uint64_t t0 = STATS ? clk() : 0;
+              if (org_tab) // one origin: (oc, c) per root stand ready (root_org)
+                trace_closest_roots<STATS, true>(S, root_org, gr, g_closest, g_best, cnt);
+              else
+                trace_closest_roots<STATS, false>(S, root_org, gr, g_closest, g_best, cnt);
+              if (STATS && wave_once()) cnt.ctrace += clk() - t0;
+            }
+            camq[rtq::kClosest][e] = g_closest;
+            camq[rtq::kBest][e] = __longlong_as_double((long long)g_best);
           }
           gen_items += rtq::kBatch;
         }
@@ -457,11 +520,30 @@ __global__ __launch_bounds__(64 * (PCW ? PCW : block_waves(F))) __attribute__((a
             key.sample = (uint32_t)ps.sample;
             ps.ray.d = v3(camq[0][e], camq[1][e], camq[2][e]);
             ps.ray.tm = camq[3][e];
-            ps.ray.o = lens ? v3(camq[4][e], camq[5][e], camq[6][e]) : ld3(Cr.center);
             ps.T = v3(1.0, 1.0, 1.0);
             ps.bounce = 0;
-            ps.active = Cr.max_depth > 0;
             if (STATS) n_samples++;
+            if (!gen_trace) { // untraced: the path loop's trace site takes it
+              ps.ray.o = lens ? v3(camq[4][e], camq[5][e], camq[6][e]) : ld3(Cr.center);
+              ps.active = Cr.max_depth > 0;
+            } else if (Cr.max_depth > 0) {
+              // traced at generation: a hit arrives parked; a miss is the
+              // background (Camera.cpp:242-243), added here with the path
+              // loop's own add of T * bg, T = 1, and its lane stays idle for
+              // the next pass of this refill loop
+              ps.ray.o = ld3(Cr.center);
+              const int eb = (int)__double_as_longlong(camq[rtq::kBest][e]);
+              if (eb >= 0) {
+                pk_closest = camq[rtq::kClosest][e];
+                pk_best = eb;
+                ps.active = true;
+              } else {
+                const V3 sky = ps.T * ld3(C.bg);
+                atomicAdd(&acc[slot * 3 + 0], sky.x);
+                atomicAdd(&acc[slot * 3 + 1], sky.y);
+                atomicAdd(&acc[slot * 3 + 2], sky.z);
+              }
+            }
           }
         }
       } else {
@@ -510,9 +592,16 @@ __global__ __launch_bounds__(64 * (PCW ? PCW : block_waves(F))) __attribute__((a
       // certain to take items: with next_item < n_items and at least
       // RT_REGEN_MIN idle lanes (a lane that just missed is idle once it has
       // added its sample below) the refill rule above passes both of its
-      // breaks, and next_item grows by the idle count.  n_items is finite, so
-      // after finitely many such trips next_item reaches it, `wait` is false
-      // and every parked lane is shaded: the loop cannot spin.
+      // breaks, and next_item grows by the idle count, at least one.  That
+      // holds of every pass of the refill loop, whatever its items turn out to
+      // be: a pass hands hits to lanes or settles misses, and advances
+      // next_item either way, so the refill loop itself ends (next_item
+      // reaches n_items, or fewer than RT_REGEN_MIN lanes are left idle).
+      // n_items is finite, so after finitely many waiting trips next_item
+      // reaches it, `wait` is false and every parked lane is shaded; a trip
+      // that does not wait shades every parked lane, and one without parked
+      // lanes traces a bounce ray or finds no active lane and leaves: the loop
+      // cannot spin.  host/rtx_batch_check.cpp replays it on the CPU.
       const bool wait = __popcll(__ballot(parked)) < kPark && next_item < n_items &&
                         __popcll(__ballot(!ps.active || done)) >= RT_REGEN_MIN(F);
       if (!wait && parked) { // ---- the one shade site

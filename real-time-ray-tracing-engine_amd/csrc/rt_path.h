@@ -631,6 +631,36 @@ RT_HD RT_FI bool sphere_root(const DSphere &s, const Ray &r, double a, double tm
   root = t;
   return true;
 }
+// The camera-origin form of sphere_root<false>.  Rays that share an origin o
+// share oc = c0 - o and c = |oc|^2 - rr of a static sphere: 9 of the 17 fp64
+// operations in front of the discriminant branch.  root_origin forms the two
+// with sphere_root's own expressions, in its operand order; sphere_root_origin
+// is sphere_root from h = dot(r.d, oc) on, operation for operation.  Both TUs
+// build without contraction, so the return value and the root are the general
+// form's bits for every ray from o (tests/test_root_origin.py).
+struct RootOrigin { // 32 B
+  V3 oc;
+  double c;
+};
+RT_HD RT_FI RootOrigin root_origin(const DRootTest &e, V3 o) {
+  V3 cc = ld3(e.c0); // sphere_center<false>
+  V3 oc = cc - o;
+  return RootOrigin{oc, len2(oc) - e.rr};
+}
+RT_HD RT_FI bool sphere_root_origin(const RootOrigin &q, const Ray &r, double a, double tmin, double tmax,
+                                    double &root, bool mk = false, double ya = 0.0) {
+  double h = dot(r.d, q.oc);
+  double disc = h * h - a * q.c;
+  if (disc < 0) return false;
+  double sq = sqrt(disc);
+  double t = mk ? div_mk(h - sq, a, ya) : (h - sq) / a;
+  if (!(tmin < t && t < tmax)) {
+    t = mk ? div_mk(h + sq, a, ya) : (h + sq) / a;
+    if (!(tmin < t && t < tmax)) return false;
+  }
+  root = t;
+  return true;
+}
 template <bool MOVING = true>
 RT_HD RT_FI void sphere_record(const DSphere &s, const Ray &r, double t, int mat,
                                               Hit &h) {
@@ -1569,6 +1599,48 @@ RT_HD RT_FI bool trace_tail(const DScene &S, const Ray &r, Hit &h, const Key &ke
   return true;
 }
 
+// One test of a root-table walk (DScene::roots: static untransformed spheres),
+// the one place it is written: root ii against ray r (|d|^2 = a, its reciprocal
+// ya) in (tmin, closest); a hit becomes the new (closest, best).  trace's flat
+// walk and the flat render loop's generation-time trace (trace_closest_roots)
+// both run it, so their tests, bounds, counters and update cannot drift apart.
+// ORG: the rays share one origin and (oc, c) per root stand ready in `tab`
+// (root_origin): sphere_root_origin in sphere_root<false>'s place, the same
+// bits.  Otherwise the 32-B test half of the DRoot, one scalar load whose
+// address depends on nothing loaded; sphere_root<false> sees the same c0 and
+// rr in the same operand order as the item walk.
+template <bool STATS, bool ORG>
+RT_HD RT_FI bool root_table_test(const DScene &S, const RT_LDS RootOrigin *tab, int ii, const Ray &r, double a,
+                                 double ya, double tmin, double &closest, int &best, Counters &cnt) {
+  if (STATS) {
+    cnt.wleaf += wave_once();
+    cnt.spheres++;
+  }
+  double t;
+  bool hit;
+  if constexpr (ORG) {
+    const RootOrigin q = tab[ii]; // one address in every lane: a broadcast read
+    hit = sphere_root_origin(q, r, a, tmin, closest, t, true, ya);
+  } else {
+    const DRootTest e = ldu<true>(&S.roots[ii].test, 0);
+    DSphere s; // c0 and rr are all the static root search reads
+    s.c0[0] = e.c0[0], s.c0[1] = e.c0[1], s.c0[2] = e.c0[2];
+    s.rr = e.rr;
+    hit = sphere_root<false>(s, r, a, tmin, closest, t, true, ya);
+  }
+  if (hit) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    // keeps the update a branch taken by the lanes that hit, as in the
+    // item walk: folded into selects it costs every test five more VALU
+    // instructions (C2 SQ_INSTS_VALU +1.4 %, profiles/flat_table_blocks.md)
+    asm volatile("");
+#endif
+    closest = t;
+    best = ii;
+  }
+  return hit;
+}
+
 // Stack entry: >= 0 inner node; < 0 a leaf ~(first << 3 | count) (DNode::entry).
 
 // Closest hit over the world BVH.  Primitive items record only (t, item) during
@@ -1752,32 +1824,13 @@ RT_HD RT_FI bool trace(const DScene &S, const Ray &r, Hit &h, const Key &key,
     // same c0 and rr in the same operand order: every t is the item walk's.
     if (RT_ROOT_TABLE_F(F) && S.n_roots) {
       const int n = S.n_roots;
-      auto load_test = [&](int ii) { return ldu<true>(&S.roots[ii].test, 0); };
-      auto test_root = [&](const DRootTest &e, int ii) {
-        if (STATS) {
-          cnt.wleaf += wave_once();
-          cnt.spheres++;
-        }
-        DSphere s; // c0 and rr are all the static root search reads
-        s.c0[0] = e.c0[0], s.c0[1] = e.c0[1], s.c0[2] = e.c0[2];
-        s.rr = e.rr;
-        double t;
-        if (sphere_root<false>(s, r, a, tmin, closest, t, true, ya)) {
-#if defined(__HIP_DEVICE_COMPILE__)
-          // keeps the update a branch taken by the lanes that hit, as in the
-          // item walk: folded into selects it costs every test five more VALU
-          // instructions (C2 SQ_INSTS_VALU +1.4 %, profiles/flat_table_blocks.md)
-          asm volatile("");
-#endif
-          closest = t;
-          if constexpr (kBoxes) cl32 = f32_up_c(closest);
-          best = ii;
-        }
-      };
       // one load per test.  Entry ii + 1 loaded before entry ii is tested, or
       // every entry of a world of at most 4 loaded before the first test: C2
       // no faster (profiles/flat_table_one_ahead_variant.patch, _up_front_).
-      for (int ii = 0; ii < n; ++ii) test_root(load_test(ii), ii);
+      for (int ii = 0; ii < n; ++ii)
+        if (root_table_test<STATS, false>(S, nullptr, ii, r, a, ya, tmin, closest, best, cnt)) {
+          if constexpr (kBoxes) cl32 = f32_up_c(closest);
+        }
     } else if (S.static_spheres) {
       for (int ii = 0; ii < S.n_root_items; ++ii) test_item_m(UTag<true>{}, UTag<false>{}, ii);
     } else {
@@ -2022,6 +2075,30 @@ RT_HD RT_FI void trace_closest(const DScene &S, const Ray &r, double &closest, i
                                RT_LDS LeafPool *pool = nullptr, const LdsPrims &lp = LdsPrims{}) {
   Hit h; // not touched
   trace<STATS, F, LP, true>(S, r, h, Key{}, 0u, stk, lnodes, cnt, pool, lp, &closest, &best);
+}
+// ... and of a root-table world alone (S.n_roots: static untransformed spheres
+// only), for the flat render loop's camera rays, which it traces where it
+// generates them (rt_kernel.hip): trace's root-table walk and nothing else of
+// trace -- the same tests in the same order against the same bound, the same
+// counters, so (closest, best) are trace_closest's.
+// ORG: the rays share one origin and (oc, c) per root stand ready in `tab`
+// (root_origin of S.roots[ii].test and that origin): sphere_root_origin in
+// sphere_root<false>'s place.  The table holds RT_ROOT_ORIGIN_MAX entries;
+// worlds of more roots take the general test (0: every world does, the A/B
+// build of the generation-time trace alone).
+#ifndef RT_ROOT_ORIGIN_MAX
+#define RT_ROOT_ORIGIN_MAX 4
+#endif
+constexpr int kRootOriginMax = RT_ROOT_ORIGIN_MAX;
+template <bool STATS, bool ORG>
+RT_HD RT_FI void trace_closest_roots(const DScene &S, const RT_LDS RootOrigin *tab, const Ray &r, double &closest,
+                                     int &best, Counters &cnt) {
+  const double tmin = 0.001; // Camera.cpp:242
+  closest = kInf;
+  best = -1;
+  const double a = len2(r.d);
+  const double ya = 1.0 / a; // one reciprocal per ray for every sphere root
+  for (int ii = 0; ii < S.n_roots; ++ii) root_table_test<STATS, ORG>(S, tab, ii, r, a, ya, tmin, closest, best, cnt);
 }
 
 // ------------------------------------------------------------ lights
