@@ -38,6 +38,7 @@
 #include <utility>
 
 #include "rt_camq.h"
+#include "rt_cull.h"
 #include "rt_kernels.h"
 #include "rt_lds_plan.h"
 #include "rt_path.h"
@@ -207,6 +208,13 @@ __device__ __forceinline__ double *out_arg(double *out) {
   }
 }
 
+// Tile culling (rt_cull.h; the plain flat world's render instances and COST
+// twin): roots a tile's camera rays cannot reach are not tested at generation,
+// and a tile that reaches none is settled without rays.  0 builds the flow
+// without it, for A/B runs (make EXTRA=-DRT_TILE_CULL=0).
+#ifndef RT_TILE_CULL
+#define RT_TILE_CULL 1
+#endif
 #ifndef RT_UNIT_TIMES
 #define RT_UNIT_TIMES 0
 #endif
@@ -379,7 +387,7 @@ __global__ __launch_bounds__(64 * (PCW ? PCW : block_waves(F))) __attribute__((a
   acc[lane * 3 + 1] = 0.0;
   acc[lane * 3 + 2] = 0.0;
 
-  const int n_items = 64 * max(0, s_count);
+  int n_items = 64 * max(0, s_count); // wave-uniform; 0 for a unit settled without rays (kCull)
   int next_item = 0; // wave-uniform head of the tile's work queue
   // camera rays generated a batch at a time by the whole wave and popped from
   // LDS (rt_camq.h): the plain flat world, every instance of it
@@ -403,18 +411,69 @@ __global__ __launch_bounds__(64 * (PCW ? PCW : block_waves(F))) __attribute__((a
   // and the generation-time trace reads them from LDS, one address in
   // every lane; a table of more than kRootOriginMax roots takes the general
   // root test there.  Both wave-uniform.
+  // root_mask (kCull: the render instances and the COST twin; the STATS
+  // instance keeps the full flow and its counters): bit ii says that a camera
+  // ray of this tile may reach root ii (rt_cull.h: a conservative reach test of
+  // the tile's bounding cone against the root, lane ii doing root ii).  It is
+  // formed where the table is (org_tab) and serves twice:
+  // the generation-time trace walks the set bits only (a skipped test is one
+  // that returned false, so (closest, best) keep their bits), and a unit whose
+  // mask is empty is settled without rays: every one of its samples is
+  // 1.0 * bg, added below by the pop's own LDS add, s_count times per pixel of
+  // the image, and the unit goes to the epilogue with an empty work queue.
+  // Bounce rays keep the full walk: their origins differ per lane.
+  constexpr bool kCull = RT_TILE_CULL != 0 && kCamq && !STATS && kRootOriginMax > 0;
+  static_assert(kRootOriginMax <= 32, "root_mask holds a bit per table entry");
   [[maybe_unused]] bool gen_trace = false, org_tab = false;
+  [[maybe_unused]] uint32_t root_mask = ~0u; // wave-uniform
   [[maybe_unused]] const RT_LDS RootOrigin *root_org = nullptr;
   if constexpr (kCamq) {
     __shared__ RootOrigin root_org_lds[kRootOriginMax > 0 ? kRootOriginMax : 1];
     root_org = (const RT_LDS RootOrigin *)&root_org_lds[0];
     gen_trace = RT_ROOT_TABLE_F(F) && n_items > rtq::kBatch && C.defocus_angle <= 0 && S.n_roots > 0;
     org_tab = gen_trace && S.n_roots <= kRootOriginMax;
-    if (org_tab) { // a unit that does not read the table pays nothing for it
+    if constexpr (!kCull) {
+      if (org_tab) { // a unit that does not read the table pays nothing for it
+        const DCamera Co = camera_fields<true>(C);
+        for (int ii = 0; ii < S.n_roots; ++ii) { // the walk's own scalar loads: no vector load opens a unit
+          const RootOrigin q = root_origin(ldu<true>(&S.roots[ii].test, 0), ld3(Co.center));
+          if (lane == 0) root_org_lds[ii] = q;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      }
+    } else if (org_tab) {
+      // the table and the mask.  Units of more than one batch only: the cone
+      // and the reach test are about 400 VALU instructions (six fp64 divisions,
+      // five square roots), which 64 batches do not notice and one batch does
+      // -- with the mask formed for one-batch units too, the one-stratum C2
+      // frames measured 0.157-0.158 -> 0.175-0.176 ms (profiles/cull_progressive_ab.log)
       const DCamera Co = camera_fields<true>(C);
+      RootOrigin mq{v3(0.0, 0.0, 0.0), 0.0}; // lane ii: root ii
+      double mrr = 0.0;
       for (int ii = 0; ii < S.n_roots; ++ii) { // the walk's own scalar loads: no vector load opens a unit
-        const RootOrigin q = root_origin(ldu<true>(&S.roots[ii].test, 0), ld3(Co.center));
+        const DRootTest e = ldu<true>(&S.roots[ii].test, 0);
+        const RootOrigin q = root_origin(e, ld3(Co.center));
         if (lane == 0) root_org_lds[ii] = q;
+        if (lane == ii) {
+          mq = q;
+          mrr = e.rr;
+        }
+      }
+      const TileCone cone = tile_cone(Co, x0, y0);
+      root_mask = (uint32_t)__ballot(lane < S.n_roots && !root_unreachable(cone, mq, mrr));
+      if (root_mask == 0 && Co.max_depth > 0) { // ---- an all-sky unit
+        const int i = x0 + (lane & 7), j = y0 + (lane >> 3);
+        if (i < Co.W && j < P.row_end) { // slots outside the image stay 0
+          const V3 sky = v3(1.0, 1.0, 1.0) * ld3(Co.bg); // the pop's T * bg, T = 1
+          for (int k = 0; k < s_count; ++k) {
+            atomicAdd(&acc[lane * 3 + 0], sky.x);
+            atomicAdd(&acc[lane * 3 + 1], sky.y);
+            atomicAdd(&acc[lane * 3 + 2], sky.z);
+          }
+        }
+        n_items = 0;
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
@@ -492,7 +551,12 @@ __global__ __launch_bounds__(64 * (PCW ? PCW : block_waves(F))) __attribute__((a
               // timed into cyc_trace like every trace; it also lies inside cyc_regen's
               // span, so the two phase shares overlap by this much
               const uint64_t t0 = STATS ? clk() : 0;
-              if (org_tab) // one origin: (oc, c) per root stand ready (root_org)
+              if constexpr (kCull) {
+                if (org_tab) // ... and only the roots this tile can reach are walked
+                  trace_closest_roots<STATS, true, true>(S, root_org, gr, g_closest, g_best, cnt, root_mask);
+                else
+                  trace_closest_roots<STATS, false>(S, root_org, gr, g_closest, g_best, cnt);
+              } else if (org_tab) // one origin: (oc, c) per root stand ready (root_org)
                 trace_closest_roots<STATS, true>(S, root_org, gr, g_closest, g_best, cnt);
               else
                 trace_closest_roots<STATS, false>(S, root_org, gr, g_closest, g_best, cnt);

@@ -2090,15 +2090,24 @@ RT_HD RT_FI void trace_closest(const DScene &S, const Ray &r, double &closest, i
 #define RT_ROOT_ORIGIN_MAX 4
 #endif
 constexpr int kRootOriginMax = RT_ROOT_ORIGIN_MAX;
-template <bool STATS, bool ORG>
+// MASKED: only the roots whose bit of `mask` is set are tested (wave-uniform: a
+// scalar branch per root; rt_cull.h forms it per tile).  A root left out is
+// one whose test returns false for this ray, so (closest, best) are the full
+// walk's.
+template <bool STATS, bool ORG, bool MASKED = false>
 RT_HD RT_FI void trace_closest_roots(const DScene &S, const RT_LDS RootOrigin *tab, const Ray &r, double &closest,
-                                     int &best, Counters &cnt) {
+                                     int &best, Counters &cnt, unsigned mask = ~0u) {
   const double tmin = 0.001; // Camera.cpp:242
   closest = kInf;
   best = -1;
   const double a = len2(r.d);
   const double ya = 1.0 / a; // one reciprocal per ray for every sphere root
-  for (int ii = 0; ii < S.n_roots; ++ii) root_table_test<STATS, ORG>(S, tab, ii, r, a, ya, tmin, closest, best, cnt);
+  for (int ii = 0; ii < S.n_roots; ++ii) {
+    if constexpr (MASKED) {
+      if (!((mask >> ii) & 1u)) continue;
+    }
+    root_table_test<STATS, ORG>(S, tab, ii, r, a, ya, tmin, closest, best, cnt);
+  }
 }
 
 // ------------------------------------------------------------ lights
