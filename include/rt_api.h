@@ -62,6 +62,11 @@
  *   rt_rotate_y_sincos
  *                     <- no counterpart, as above: these set translate / rotate_y objects and
  *                        move quads of a live scene; media boxes and the world BVH follow
+ *   rt_scene_pose_device / rt_motion_device / rt_temporal_motion_device /
+ *   rt_temporal_variance_motion_device
+ *                     <- no counterpart, as above: per pixel, where the surface under it stood
+ *                        before those edits, and the reprojection read there, so that a moved
+ *                        object does not cost the display its history
  *   rt_last_error     <- replaces CUDA_CHECK's exit() and the converters' exceptions
  *                        (CudaMemoryUtility.cuh:9-15, HittableConverter.cuh:103-108): errors are
  *                        returned as negative codes, never thrown or exit()ed across the ABI.
@@ -1283,6 +1288,87 @@ int rt_multi_radiance(rt_multi *multi, int64_t n, const rt_ray *rays, const rt_r
    the frame, stratum outside [0, sqrt_spp^2). */
 int rt_camera_rays(const rt_frame *frame, uint64_t seed, int32_t stratum, int32_t row_begin, int32_t row_end,
                    rt_ray *rays);
+
+/* ---- object motion vectors (functions and one struct added under ABI 5: no
+   struct or signature above changed) ---------------------------------------
+   rt_temporal_device reprojects along the camera only: after an edit
+   (rt_scene_move_spheres, rt_scene_set_transforms, rt_scene_move_quads) a
+   history of the old scene would be blended onto the moved objects.  A pose is
+   a snapshot of what those edits write; rt_motion_device gives, per pixel,
+   where the surface under it stood at an earlier pose; the _motion forms of
+   the temporal calls reproject along camera and object motion together
+   (rtx/temporal.py TemporalDisplay.edited drives all of it; DESIGN.md "Object
+   motion vectors").  Constant media carry no motion. */
+
+/* Bytes of one pose of this scene: a multiple of 256, at least 256. */
+int rt_scene_pose_bytes(const rt_scene *scene, int64_t *bytes);
+
+/* device_pose = the scene's movable state as it stands at this point of the
+   scene's launch chain, after every edit queued before the call: (a, b, c) of
+   every transform record, c0 of every sphere record and Q of every quad record,
+   three doubles each.  The layout is the library's own: only rt_motion_device
+   reads it.  It is indexed by table record, not by world item:
+   rt_scene_rebuild_bvh permutes the items and leaves the primitive tables where
+   they are, so a pose outlives a rebuild.  A pose belongs to the scene it was
+   taken from; the caller owns the buffer, the library keeps nothing.
+   Asynchronous on hip_stream and a link of the scene's launch chain, like
+   rt_scene_move_spheres_device.  RT_ERR_INVALID, before anything is queued: a
+   null scene, a null device_pose or one that is not 256-B aligned. */
+int rt_scene_pose_device(rt_scene *scene, void *device_pose, void *hip_stream);
+
+typedef struct rt_motion {
+  double d[3];  /* where the surface point under the pixel centre was at the pose, minus where it is */
+  double dn[3]; /* its unit normal then, minus now */
+  double t;     /* rt_trace's t of the pixel-centre ray; +inf: a miss */
+  int32_t object, chain_object; /* rt_ray_hit's; -1, -1 for a miss */
+} rt_motion; /* 64 B; a miss: d = dn = 0, t = +inf, object = chain_object = -1 */
+
+/* device_motion[j * image_width + i] = the motion of the surface under pixel
+   (i, j) since device_pose_prev was taken.  The ray is rt_pixel_ray(frame, i,
+   j); t, object and chain_object are the bytes rt_trace_device writes for it
+   (constant media are passed through).  The hit is carried into the winning
+   item's local frame (the current transform chain), its offset q from the
+   primitive's anchor (c0 of a sphere, Q of a quad) and its local normal are
+   placed twice by the same operations -- anchor + q, then the chain innermost
+   first -- once with the scene's current tables and once with the pose's values
+   of the same records: d and dn are the differences.  An object nothing moved
+   therefore has d = dn = +0 exactly.  One lane per pixel, every record written
+   once with plain stores; uses none of the scene's scratch and allocates
+   nothing.  Asynchronous on hip_stream, a link of the scene's launch chain.
+   RT_ERR_INVALID, before anything is queued: a null argument; an empty frame;
+   a device_pose_prev that is not 256-B aligned; a device_motion that is not
+   8-B aligned. */
+int rt_motion_device(rt_scene *scene, const rt_frame *frame, const void *device_pose_prev,
+                     rt_motion *device_motion, void *hip_stream);
+
+/* rt_temporal_device with object motion: device_motion is rt_motion_device's
+   plane for frame_now and the pose device_history_prev was committed at.  A
+   pixel whose guide normal is a surface's (|n|^2 >= 0.25), whose record is a
+   hit (object >= 0) and whose d and dn are not all zero substitutes
+   P_m = P + d for P in the projection (v, den, x, y, r) and in the plane test,
+   n_m = n + dn for n in the normal test, and n_m / |n_m| for n / |n| as the
+   plane's normal.  Everything written is unchanged: geo = (n, z) is the
+   current pose's; the blend and the counts are rt_temporal_device's.  Every
+   other pixel (media included) takes rt_temporal_device's path: an all-zero
+   plane gives that function's outputs bit for bit.  A non-finite d gives a NaN
+   x, which fails the range test: no history.  device_motion is only read and
+   may overlap no output.  Refusals: rt_temporal_device's, and a null or
+   overlapping device_motion. */
+int rt_temporal_motion_device(const rt_frame *frame_now, const double *device_rgb, double rgb_scale,
+                              const int32_t *device_tile_strata, int32_t strata_now,
+                              const double *device_guides, int32_t guide_strata,
+                              const rt_frame *frame_prev, const void *device_history_prev,
+                              const rt_motion *device_motion, const rt_temporal_params *params,
+                              void *device_history_out, double *device_out, void *hip_stream);
+
+/* rt_temporal_variance_device with object motion, in the same way. */
+int rt_temporal_variance_motion_device(const rt_frame *frame_now, const double *device_rgb, double rgb_scale,
+                                       const int32_t *device_tile_strata, int32_t strata_now,
+                                       const double *device_guides, int32_t guide_strata,
+                                       const rt_frame *frame_prev, const void *device_history_prev,
+                                       const rt_motion *device_motion, const double *device_variance_now,
+                                       const rt_temporal_params *params, void *device_history_out,
+                                       double *device_out, double *device_variance_out, void *hip_stream);
 
 /* ---- guided sampling (one function added under ABI 5: no struct or signature
    above changed) ------------------------------------------------------------

@@ -120,6 +120,7 @@ struct rt_scene {
   // whose block holds its creation tree and no more.
   std::vector<DItem> compile_items;
   int32_t n_spheres = 0, n_perlin = 0;
+  int32_t n_xforms = 0, n_quads = 0; // with n_spheres: a pose's layout (rt_live.h PoseCounts)
   int32_t bvh_depth = 0, bvh_depth4 = 0;
   size_t node_room = 0; // bytes of the node range d.nodes points into
   struct Rebuild { // offsets into `rebuild`; the builder and the collapse run in turn and share temp
@@ -601,6 +602,8 @@ static void keep_movable(rt_scene *s, const rt_scene_desc *desc, rtx::HostScene 
   s->n_items = (int32_t)H.items.size();
   s->n_spheres = (int32_t)H.spheres.size();
   s->n_perlin = (int32_t)H.perlin.size();
+  s->n_xforms = (int32_t)H.xforms.size();
+  s->n_quads = (int32_t)H.quads.size();
   s->bvh_arity = H.bvh_arity;
   s->bvh_depth = H.bvh_depth;
   s->bvh_depth4 = H.bvh_depth4;
@@ -1524,6 +1527,116 @@ int rt_temporal_variance_device(const rt_frame *f, const double *device_rgb, dou
                                               device_variance_now, &q, device_history_out, device_out,
                                               device_variance_out, (hipStream_t)hip_stream);
   if (e != hipSuccess) return hip_err(e, "temporal variance launch");
+  return RT_OK;
+}
+
+// ---------------------------------------------------------------- object motion vectors
+static rt_live::PoseCounts pose_counts(const rt_scene *s) {
+  return rt_live::PoseCounts{s->n_xforms, s->n_spheres, s->n_quads, 0};
+}
+
+int rt_scene_pose_bytes(const rt_scene *s, int64_t *bytes) {
+  if (!s || !bytes) return set_err(RT_ERR_INVALID, "null argument");
+  *bytes = rt_live::pose_bytes(pose_counts(s));
+  return RT_OK;
+}
+
+// One pack kernel on `st`: it reads the tables the edits write, so it is a link of the chain.
+int rt_scene_pose_device(rt_scene *s, void *device_pose, void *hip_stream) {
+  if (!s) return set_err(RT_ERR_INVALID, "null scene");
+  if (!device_pose) return set_err(RT_ERR_INVALID, "null device_pose");
+  if (((uintptr_t)device_pose & 255) != 0) return set_err(RT_ERR_INVALID, "a pose must be 256-B aligned");
+  DeviceGuard g(s->device);
+  hipStream_t st = (hipStream_t)hip_stream;
+  int rc = order_after_last(s, st);
+  if (rc) return rc;
+  const rt_live::PoseCounts c = pose_counts(s);
+  const DScene &d = s->ds;
+  hipError_t e = rtk_pose(&c, d.xforms, d.spheres, d.quads, (double *)device_pose, st);
+  rc = mark_last(s, st);
+  if (e != hipSuccess) return hip_err(e, "pose kernel launch");
+  return rc;
+}
+
+int rt_motion_device(rt_scene *s, const rt_frame *f, const void *device_pose_prev, rt_motion *device_motion,
+                     void *hip_stream) {
+  if (!s || !f || !device_pose_prev || !device_motion) return set_err(RT_ERR_INVALID, "null argument");
+  int64_t tiles = 0;
+  if (int rc = frame_tiles(f, tiles)) return rc;
+  if (((uintptr_t)device_pose_prev & 255) != 0) return set_err(RT_ERR_INVALID, "a pose must be 256-B aligned");
+  if (((uintptr_t)device_motion & 7) != 0) return set_err(RT_ERR_INVALID, "device_motion must be 8-B aligned");
+  DeviceGuard g(s->device);
+  hipStream_t st = (hipStream_t)hip_stream;
+  int rc = order_after_last(s, st);
+  if (rc) return rc;
+  const rt_live::PoseCounts c = pose_counts(s);
+  hipError_t e = rtk_launch_motion(&s->ds, s->xf_obj, f, &c, (const double *)device_pose_prev, device_motion, st);
+  if (e != hipSuccess) return hip_err(e, "motion kernel launch");
+  return mark_last(s, st);
+}
+
+// what the _motion forms refuse beyond their parents: a null plane, or one an output overlaps
+static int motion_args(const rt_frame *f, const rt_motion *device_motion, const void *device_history_out, size_t hb,
+                       const double *device_out, const double *device_variance_out) {
+  if (!device_motion) return set_err(RT_ERR_INVALID, "null device_motion");
+  const size_t px = (size_t)f->image_width * f->image_height;
+  const Span m(device_motion, px * sizeof(rt_motion));
+  if (overlaps(m, Span(device_history_out, hb))) return set_err(RT_ERR_INVALID, "device_motion overlaps device_history_out");
+  if (overlaps(m, Span(device_out, px * 3 * sizeof(double)))) return set_err(RT_ERR_INVALID, "device_motion overlaps device_out");
+  if (device_variance_out && overlaps(m, Span(device_variance_out, px * sizeof(double))))
+    return set_err(RT_ERR_INVALID, "device_motion overlaps device_variance_out");
+  return RT_OK;
+}
+
+int rt_temporal_motion_device(const rt_frame *f, const double *device_rgb, double rgb_scale,
+                              const int32_t *device_tile_strata, int32_t strata_now, const double *device_guides,
+                              int32_t guide_strata, const rt_frame *frame_prev, const void *device_history_prev,
+                              const rt_motion *device_motion, const rt_temporal_params *params,
+                              void *device_history_out, double *device_out, void *hip_stream) {
+  int64_t tiles = 0;
+  if (int rc = frame_tiles(f, tiles)) return rc;
+  const size_t hb = rtk_history_bytes(f->image_width, f->image_height);
+  rt_temporal_params q{};
+  if (int rc = temporal_args(f, device_rgb, device_tile_strata, strata_now, device_guides, guide_strata, frame_prev,
+                             device_history_prev, params, device_history_out, device_out, hb, q))
+    return rc;
+  if (int rc = motion_args(f, device_motion, device_history_out, hb, device_out, nullptr)) return rc;
+  hipError_t e = rtk_launch_temporal_motion(f, device_rgb, rgb_scale, device_tile_strata, strata_now, device_guides,
+                                            guide_strata, frame_prev, device_history_prev, device_motion, &q,
+                                            device_history_out, device_out, (hipStream_t)hip_stream);
+  if (e != hipSuccess) return hip_err(e, "temporal motion launch");
+  return RT_OK;
+}
+
+int rt_temporal_variance_motion_device(const rt_frame *f, const double *device_rgb, double rgb_scale,
+                                       const int32_t *device_tile_strata, int32_t strata_now,
+                                       const double *device_guides, int32_t guide_strata, const rt_frame *frame_prev,
+                                       const void *device_history_prev, const rt_motion *device_motion,
+                                       const double *device_variance_now, const rt_temporal_params *params,
+                                       void *device_history_out, double *device_out, double *device_variance_out,
+                                       void *hip_stream) {
+  int64_t tiles = 0;
+  if (int rc = frame_tiles(f, tiles)) return rc;
+  if (!device_variance_now || !device_variance_out) return set_err(RT_ERR_INVALID, "null argument");
+  const size_t hb = rtk_history_variance_bytes(f->image_width, f->image_height);
+  rt_temporal_params q{};
+  if (int rc = temporal_args(f, device_rgb, device_tile_strata, strata_now, device_guides, guide_strata, frame_prev,
+                             device_history_prev, params, device_history_out, device_out, hb, q))
+    return rc;
+  const size_t px = (size_t)f->image_width * f->image_height;
+  const Span vout(device_variance_out, px * sizeof(double));
+  if (overlaps(vout, Span(device_history_out, hb)) || overlaps(vout, Span(device_history_prev, hb)))
+    return set_err(RT_ERR_INVALID, "device_variance_out overlaps a history");
+  if (overlaps(vout, Span(device_variance_now, px * sizeof(double))))
+    return set_err(RT_ERR_INVALID, "device_variance_out overlaps device_variance_now");
+  if (overlaps(vout, Span(device_out, px * 3 * sizeof(double))))
+    return set_err(RT_ERR_INVALID, "device_variance_out overlaps device_out");
+  if (int rc = motion_args(f, device_motion, device_history_out, hb, device_out, device_variance_out)) return rc;
+  hipError_t e = rtk_launch_temporal_variance_motion(f, device_rgb, rgb_scale, device_tile_strata, strata_now,
+                                                     device_guides, guide_strata, frame_prev, device_history_prev,
+                                                     device_motion, device_variance_now, &q, device_history_out,
+                                                     device_out, device_variance_out, (hipStream_t)hip_stream);
+  if (e != hipSuccess) return hip_err(e, "temporal variance motion launch");
   return RT_OK;
 }
 

@@ -1,6 +1,6 @@
 // rt_kernels.h — every rtk_* launcher, declared once: included by the files
 // that define them (rt_kernel.hip, rt_frame.hip, rt_adaptive.hip, rt_guides.hip,
-// rt_denoise.hip, rt_temporal.hip, rt_bvh_build.hip, rt_bvh_sah.hip, rt_collapse.hip, rt_refit.hip, rt_query.hip, rt_occlusion.hip, rt_radiance.hip) and by their caller (rt_api.cpp), so a
+// rt_denoise.hip, rt_temporal.hip, rt_bvh_build.hip, rt_bvh_sah.hip, rt_collapse.hip, rt_refit.hip, rt_query.hip, rt_occlusion.hip, rt_radiance.hip, rt_motion.hip) and by their caller (rt_api.cpp), so a
 // definition whose parameter list drifts from its callers' no longer compiles.
 #ifndef RT_KERNELS_H
 #define RT_KERNELS_H
@@ -66,6 +66,12 @@ hipError_t rtk_launch_guides(const DScene *S, const DCamera *C, const DLaunch *P
 hipError_t rtk_launch_trace(const DScene *S, const int32_t *xf_obj, int64_t n, const rt_ray *rays,
                             rt_ray_hit *hits, hipStream_t stream);
 
+// ---- rt_motion.hip: motion[j * W + i] = the motion of the surface under pixel (i, j) of the frame
+// since `pose_prev` was taken (rt_motion.h; c: the pose's layout, rt_live.h; an empty frame queues nothing)
+hipError_t rtk_launch_motion(const DScene *S, const int32_t *xf_obj, const rt_frame *frame,
+                             const rt_live::PoseCounts *c, const double *pose_prev, rt_motion *motion,
+                             hipStream_t stream);
+
 // ---- rt_occlusion.hip: occluded[k] = 1 where something stands in (0.001, t_max] of rays[k], else 0,
 // k in [0, n): one byte each (rt_occlusion.h; n <= 0 queues nothing)
 hipError_t rtk_launch_occluded(const DScene *S, int64_t n, const rt_ray *rays, uint8_t *occluded,
@@ -117,6 +123,18 @@ hipError_t rtk_launch_temporal_variance(const rt_frame *now, const double *rgb, 
                                         int guide_strata, const rt_frame *prev, const void *history_prev,
                                         const double *variance_now, const rt_temporal_params *params,
                                         void *history_out, double *out, double *variance_out, hipStream_t stream);
+// the _motion pair: `motion` is rt_motion_device's plane (not null)
+hipError_t rtk_launch_temporal_variance_motion(const rt_frame *now, const double *rgb, double scale,
+                                               const int32_t *tile_strata, int strata_now, const double *guides,
+                                               int guide_strata, const rt_frame *prev, const void *history_prev,
+                                               const rt_motion *motion, const double *variance_now,
+                                               const rt_temporal_params *params, void *history_out, double *out,
+                                               double *variance_out, hipStream_t stream);
+hipError_t rtk_launch_temporal_motion(const rt_frame *now, const double *rgb, double scale,
+                                      const int32_t *tile_strata, int strata_now, const double *guides,
+                                      int guide_strata, const rt_frame *prev, const void *history_prev,
+                                      const rt_motion *motion, const rt_temporal_params *params, void *history_out,
+                                      double *out, hipStream_t stream);
 size_t rtk_history_bytes(int W, int H);
 hipError_t rtk_launch_temporal(const rt_frame *now, const double *rgb, double scale, const int32_t *tile_strata,
                                int strata_now, const double *guides, int guide_strata, const rt_frame *prev,
@@ -186,6 +204,9 @@ struct LiveEdit {
 };
 hipError_t rtk_set_transforms(const LiveEdit *e, hipStream_t st);
 hipError_t rtk_move_quads(const LiveEdit *e, hipStream_t st);
+// the pose of these tables (rt_live.h: pose_bytes(c) bytes at `pose`), one thread per record
+hipError_t rtk_pose(const rt_live::PoseCounts *c, const DXform *xforms, const DSphere *spheres, const DQuad *quads,
+                    double *pose, hipStream_t st);
 // each world medium's box from the tables (rt_refit.h medium_box) into mbox (6 floats per medium)
 hipError_t rtk_medium_boxes(const DItem *mitems, int n_mitems, const DMedium *media, const DItem *bitems,
                             const DSphere *spheres, const DQuad *quads, const DXform *xforms, float *mbox,

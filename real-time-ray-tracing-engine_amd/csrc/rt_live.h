@@ -82,5 +82,42 @@ RT_REFIT_HD void apply_quad(DQuad &q, const double *corner, double D) {
   q.D = D;
 }
 
+// A pose (rt_scene_pose_device): everything the edits above and a sphere move
+// can write, three doubles per table record -- (a, b, c) of the xforms[]
+// records, then c0 of the spheres[] records, then Q of the quads[] records.
+// Indexed by table record: a rebuild permutes the items, never these tables
+// (rt_api.cpp rt_scene_rebuild_bvh commits nodes and items only).  D of a quad
+// follows from Q and is not part of it; a rotate_y record's c is carried along
+// unread.  Read by rt_motion.h alone.
+struct PoseCounts {
+  int32_t n_xforms, n_spheres, n_quads, pad_;
+};
+RT_REFIT_HD int64_t pose_records(const PoseCounts &c) { return (int64_t)c.n_xforms + c.n_spheres + c.n_quads; }
+RT_REFIT_HD int64_t pose_bytes(const PoseCounts &c) { // a multiple of 256, >= 256
+  const int64_t b = 3 * (int64_t)sizeof(double) * pose_records(c);
+  return b < 256 ? 256 : (b + 255) & ~(int64_t)255;
+}
+RT_REFIT_HD const double *pose_xform(const PoseCounts &, const double *pose, int rec) { return pose + 3 * (int64_t)rec; }
+RT_REFIT_HD const double *pose_sphere(const PoseCounts &c, const double *pose, int rec) {
+  return pose + 3 * ((int64_t)c.n_xforms + rec);
+}
+RT_REFIT_HD const double *pose_quad(const PoseCounts &c, const double *pose, int rec) {
+  return pose + 3 * ((int64_t)c.n_xforms + c.n_spheres + rec);
+}
+// record k in [0, pose_records) of the pose of these tables
+RT_REFIT_HD void pose_pack(const PoseCounts &c, int64_t k, const DXform *xforms, const DSphere *spheres,
+                           const DQuad *quads, double out[3]) {
+  if (k < c.n_xforms) {
+    const DXform &x = xforms[k];
+    out[0] = x.a, out[1] = x.b, out[2] = x.c;
+  } else if (k < (int64_t)c.n_xforms + c.n_spheres) {
+    const DSphere &s = spheres[k - c.n_xforms];
+    out[0] = s.c0[0], out[1] = s.c0[1], out[2] = s.c0[2];
+  } else {
+    const DQuad &q = quads[k - c.n_xforms - c.n_spheres];
+    out[0] = q.Q[0], out[1] = q.Q[1], out[2] = q.Q[2];
+  }
+}
+
 } // namespace rt_live
 #endif

@@ -168,6 +168,16 @@ __global__ void quad_apply(LiveEdit e) {
   rt_live::apply_quad(e.quads[e.index.quad_of[e.ids[j]]], c, D);
 }
 
+// A pose (rt_live.h): one thread per table record, three plain 8-B stores.
+__global__ void pose_pack(rt_live::PoseCounts c, const DXform *xforms, const DSphere *spheres, const DQuad *quads,
+                          double *pose) {
+  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= rt_live::pose_records(c)) return;
+  double v[3];
+  rt_live::pose_pack(c, k, xforms, spheres, quads, v);
+  for (int a = 0; a < 3; ++a) pose[3 * k + a] = v[a];
+}
+
 __global__ void medium_boxes(const DItem *mitems, int n_mitems, const DMedium *media, const DItem *bitems,
                              const DSphere *spheres, const DQuad *quads, const DXform *xforms, float *mbox) {
   const int m = blockIdx.x * blockDim.x + threadIdx.x;
@@ -287,6 +297,15 @@ extern "C" hipError_t rtk_move_quads(const LiveEdit *e, hipStream_t st) {
   if (err != hipSuccess) return err;
   hipLaunchKernelGGL(quad_count, dim3(grid(e->n)), dim3(B), 0, st, *e);
   hipLaunchKernelGGL(quad_apply, dim3(grid(e->n)), dim3(B), 0, st, *e);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t rtk_pose(const rt_live::PoseCounts *c, const DXform *xforms, const DSphere *spheres,
+                               const DQuad *quads, double *pose, hipStream_t st) {
+  const int64_t n = rt_live::pose_records(*c);
+  if (n <= 0) return hipSuccess;
+  if (n >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(pose_pack, dim3(grid((size_t)n)), dim3(B), 0, st, *c, xforms, spheres, quads, pose);
   return hipGetLastError();
 }
 

@@ -95,12 +95,21 @@ RT_HD RT_FI bool finite1(double x) { return fabs(x) < __builtin_huge_val(); }
 // ovar are the histories' third planes (fp32 scalars; pvar null with pcol),
 // v_now / v_out [H][W] double planes.  Without VAR none of them is touched and
 // the colour arithmetic is the same operations in the same order.
-template <bool VAR>
+// MOT (rt_temporal_motion_device, rt_temporal_variance_motion_device; DESIGN.md
+// §7q): `motion` is rt_motion_device's plane.  A surface pixel (|n|^2 >= 0.25)
+// whose record is a hit and whose d and dn are not all zero projects P + d, tests
+// n + dn against the taps' normals and the taps' points against the plane through
+// P + d with normal (n + dn) / |n + dn|; every other pixel takes P and n
+// themselves (selected, not added: P + 0 could turn a -0 into +0), so an all-zero
+// plane gives the bits of the form without MOT.  What is written (geo = (n, z)
+// included) is the current pose's.  Without MOT `motion` is not touched.
+template <bool VAR, bool MOT = false>
 RT_HD RT_FI void temporal_core(const Cam &now, const Cam &prev, int W, int H, int i, int j, const double *rgb,
                                  double scale, const int32_t *tile_strata, int strata_now,
                                  const double *guides, double g, const F4 *pcol, const F4 *pgeo,
                                  const float *pvar, const Coef &K, F4 *ocol, F4 *ogeo, double *out,
-                                 const double *v_now, float *ovar, double *v_out) {
+                                 const double *v_now, float *ovar, double *v_out,
+                                 const rt_motion *motion = nullptr) {
   const int64_t p = (int64_t)j * W + i;
   double s = scale, n_c = (double)strata_now;
   if (tile_strata != nullptr) { // rt_to_bytes_tiles_device's scale; the tile's own count
@@ -122,7 +131,19 @@ RT_HD RT_FI void temporal_core(const Cam &now, const Cam &prev, int W, int H, in
 
   double n_h = 0.0, eh[3] = {0.0, 0.0, 0.0}, v_h = 0.0;
   if (pcol != nullptr && h >= K.hit_min) {
-    const D3 P = centre_point(now, i, j, z);
+    D3 P = centre_point(now, i, j, z);
+    D3 nt = n; // the normal the taps' normals are held to
+    bool moved = false;
+    if (MOT) {
+      const rt_motion m = motion[p];
+      const D3 d = D3{m.d[0], m.d[1], m.d[2]}, dn = D3{m.dn[0], m.dn[1], m.dn[2]};
+      moved = dot(n, n) >= 0.25 && m.object >= 0 &&
+              (d.x != 0.0 || d.y != 0.0 || d.z != 0.0 || dn.x != 0.0 || dn.y != 0.0 || dn.z != 0.0);
+      if (moved) {
+        P = P + d;
+        nt = n + dn;
+      }
+    }
     const D3 v = P - prev.c;
     const D3 Np = cross(prev.du, prev.dv);
     const double num = dot(prev.p00 - prev.c, Np), den = dot(v, Np);
@@ -138,7 +159,10 @@ RT_HD RT_FI void temporal_core(const Cam &now, const Cam &prev, int W, int H, in
         const double wx = x - fx, wy = y - fy;
         const double nn = dot(n, n);
         const bool plane = nn >= 0.25;
-        const D3 nu = plane ? (1.0 / sqrt(nn)) * n : n;
+        D3 nu = plane ? (1.0 / sqrt(nn)) * n : n;
+        if (MOT) {
+          if (moved) nu = (1.0 / sqrt(dot(nt, nt))) * nt;
+        }
         double Wv = 0.0, cnt = 0.0, se[3] = {0.0, 0.0, 0.0}, sv = 0.0;
         for (int b = 0; b < 2; ++b) {
           const int qy = y0 + b;
@@ -151,7 +175,7 @@ RT_HD RT_FI void temporal_core(const Cam &now, const Cam &prev, int W, int H, in
             const F4 cq = pcol[t], gq = pgeo[t];
             bool ok = cq.w > 0.0f && finite1((double)cq.x) && finite1((double)cq.y) && finite1((double)cq.z);
             if (K.normal_on) {
-              const D3 dn = n - D3{(double)gq.x, (double)gq.y, (double)gq.z};
+              const D3 dn = nt - D3{(double)gq.x, (double)gq.y, (double)gq.z};
               ok = ok && dot(dn, dn) <= K.sigma_n2;
             }
             if (K.depth_on) {
@@ -229,6 +253,24 @@ RT_HD RT_FI void temporal_variance_pixel(const Cam &now, const Cam &prev, int W,
                                            float *ovar, double *out, const double *v_now, double *v_out) {
   temporal_core<true>(now, prev, W, H, i, j, rgb, scale, tile_strata, strata_now, guides, g, pcol, pgeo, pvar, K,
                       ocol, ogeo, out, v_now, ovar, v_out);
+}
+
+// The two pixels above with object motion (temporal_core's MOT).
+RT_HD RT_FI void temporal_motion_pixel(const Cam &now, const Cam &prev, int W, int H, int i, int j, const double *rgb,
+                                         double scale, const int32_t *tile_strata, int strata_now,
+                                         const double *guides, double g, const F4 *pcol, const F4 *pgeo,
+                                         const rt_motion *motion, const Coef &K, F4 *ocol, F4 *ogeo, double *out) {
+  temporal_core<false, true>(now, prev, W, H, i, j, rgb, scale, tile_strata, strata_now, guides, g, pcol, pgeo,
+                             nullptr, K, ocol, ogeo, out, nullptr, nullptr, nullptr, motion);
+}
+RT_HD RT_FI void temporal_variance_motion_pixel(const Cam &now, const Cam &prev, int W, int H, int i, int j,
+                                                  const double *rgb, double scale, const int32_t *tile_strata,
+                                                  int strata_now, const double *guides, double g, const F4 *pcol,
+                                                  const F4 *pgeo, const float *pvar, const rt_motion *motion,
+                                                  const Coef &K, F4 *ocol, F4 *ogeo, float *ovar, double *out,
+                                                  const double *v_now, double *v_out) {
+  temporal_core<true, true>(now, prev, W, H, i, j, rgb, scale, tile_strata, strata_now, guides, g, pcol, pgeo, pvar,
+                            K, ocol, ogeo, out, v_now, ovar, v_out, motion);
 }
 
 } // namespace rtt

@@ -244,6 +244,12 @@ class RayHit(C.Structure):
                 ("material", C.c_int32), ("front", C.c_int32)]
 
 
+class Motion(C.Structure):
+    """rt_motion (64 B).  A miss: d = dn = 0, t = +inf, object = chain_object = -1."""
+    _fields_ = [("d", C.c_double * 3), ("dn", C.c_double * 3), ("t", C.c_double),
+                ("object", C.c_int32), ("chain_object", C.c_int32)]
+
+
 class RadianceParams(C.Structure):
     """rt_radiance_params (56 B)."""
     _fields_ = [("seed", C.c_uint64), ("first_key", C.c_uint32), ("first_sample", C.c_int32),
@@ -285,4 +291,6 @@ EXPORTS = (
     "rt_trace_device", "rt_trace", "rt_multi_trace", "rt_pixel_ray",
     "rt_occluded_device", "rt_occluded", "rt_multi_occluded", "rt_segment_ray",
     "rt_radiance_device", "rt_radiance", "rt_multi_radiance", "rt_camera_rays",
+    "rt_scene_pose_bytes", "rt_scene_pose_device", "rt_motion_device",
+    "rt_temporal_motion_device", "rt_temporal_variance_motion_device",
 )

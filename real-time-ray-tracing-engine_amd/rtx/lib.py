@@ -89,6 +89,16 @@ def load():
                                               C.c_void_p, C.c_int32, P(abi.Frame), C.c_void_p, C.c_void_p,
                                               P(abi.TemporalParams), C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p]
+    L.rt_scene_pose_bytes.argtypes = [C.c_void_p, P(C.c_int64)]
+    L.rt_scene_pose_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rt_motion_device.argtypes = [C.c_void_p, P(abi.Frame), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rt_temporal_motion_device.argtypes = [P(abi.Frame), C.c_void_p, C.c_double, C.c_void_p, C.c_int32, C.c_void_p,
+                                            C.c_int32, P(abi.Frame), C.c_void_p, C.c_void_p, P(abi.TemporalParams),
+                                            C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rt_temporal_variance_motion_device.argtypes = [P(abi.Frame), C.c_void_p, C.c_double, C.c_void_p, C.c_int32,
+                                                     C.c_void_p, C.c_int32, P(abi.Frame), C.c_void_p, C.c_void_p,
+                                                     C.c_void_p, P(abi.TemporalParams), C.c_void_p, C.c_void_p,
+                                                     C.c_void_p, C.c_void_p]
     L.rt_denoise_given_variance_device.argtypes = [P(abi.Frame), C.c_void_p, C.c_double, C.c_void_p, C.c_void_p,
                                                    C.c_int32, C.c_void_p, P(abi.DenoiseVarianceParams),
                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

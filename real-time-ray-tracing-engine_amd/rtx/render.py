@@ -64,6 +64,8 @@ def describe_quads(scene, ids, corners):
 RAY_DTYPE = np.dtype([("origin", "<f8", 3), ("direction", "<f8", 3), ("time", "<f8"), ("t_max", "<f8")])
 HIT_DTYPE = np.dtype([("t", "<f8"), ("p", "<f8", 3), ("n", "<f8", 3), ("object", "<i4"),
                       ("chain_object", "<i4"), ("material", "<i4"), ("front", "<i4")])
+# rt_motion as a NumPy record (the layout of abi.Motion)
+MOTION_DTYPE = np.dtype([("d", "<f8", 3), ("dn", "<f8", 3), ("t", "<f8"), ("object", "<i4"), ("chain_object", "<i4")])
 
 
 def ray_array(rays):
@@ -304,8 +306,9 @@ class Renderer:
         refitted on the device.  Synchronous.  The SceneDescription the
         renderer was made from is updated too, so a later Renderer(scene) or
         dump_scene(scene) describes the moved scene.  Whatever was accumulated
-        or displayed before the move (progressive.py, adaptive.py, the display
-        classes) describes the old scene: reset() it."""
+        before the move (progressive.py, adaptive.py, the display classes)
+        describes the old scene: reset() it -- the temporal displays through
+        edited(), which keeps their history along the objects' motion."""
         ids, centres = _move_arrays(ids, centres)
         check(self.lib.rt_scene_move_spheres(self.handle, len(ids), ids.ctypes.data_as(C.POINTER(C.c_int32)),
                                              centres.ctypes.data_as(C.POINTER(C.c_double))))
@@ -330,8 +333,9 @@ class Renderer:
         `values` ([n, 3]: an offset, or (sin, cos, ignored) -- rotate_y_row
         gives the row of an angle); every medium's world box and the world BVH
         follow on the device.  Synchronous.  The SceneDescription follows as
-        with move_spheres, and as there whatever was accumulated or displayed
-        before describes the old scene: reset() it."""
+        with move_spheres, and as there whatever was accumulated before
+        describes the old scene: reset() it, the temporal displays through
+        edited()."""
         describe_transforms(self.scene_desc, *self._edit(self.lib.rt_scene_set_transforms, ids, values))
 
     def set_transforms_device(self, ids_ptr, values_ptr, n, stream_ptr=None):
@@ -379,6 +383,30 @@ class Renderer:
         every edit queued before it."""
         check(self.lib.rt_trace_device(self.handle, int(n), C.c_void_p(rays_ptr), C.c_void_p(hits_ptr),
                                        C.c_void_p(stream_ptr or 0)))
+
+    def pose_bytes(self):
+        """rt_scene_pose_bytes: the size of one pose of this scene (a multiple of 256)."""
+        n = C.c_int64(0)
+        check(self.lib.rt_scene_pose_bytes(self.handle, C.byref(n)))
+        return n.value
+
+    def pose_device(self, ptr, stream_ptr=None):
+        """rt_scene_pose_device: the scene's movable state -- what move_spheres,
+        set_transforms and move_quads write -- as it stands after every edit
+        queued so far, into the device buffer of pose_bytes() at `ptr` (256-B
+        aligned), asynchronously on `stream_ptr`.  Only motion_device reads it;
+        it survives rebuild_bvh()."""
+        check(self.lib.rt_scene_pose_device(self.handle, C.c_void_p(ptr), C.c_void_p(stream_ptr or 0)))
+
+    def motion_device(self, frame, pose_ptr, out_ptr, stream_ptr=None):
+        """rt_motion_device: per pixel of `frame`, row-major, one MOTION_DTYPE
+        record into the device array at `out_ptr` -- where the surface under the
+        pixel centre stood when the pose at `pose_ptr` was taken, minus where it
+        is (d), the same for its unit normal (dn), and trace's t, object and
+        chain_object of pixel_ray(frame, i, j).  Asynchronous on `stream_ptr`,
+        after every edit queued before it."""
+        check(self.lib.rt_motion_device(self.handle, C.byref(frame), C.c_void_p(pose_ptr), C.c_void_p(out_ptr),
+                                        C.c_void_p(stream_ptr or 0)))
 
     def pick(self, frame, x, y):
         """What lies under the point (x, y) of the frame: the hit of

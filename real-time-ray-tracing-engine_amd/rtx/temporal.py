@@ -74,9 +74,30 @@ bit for bit; added per pixel:
 
 rtx.denoise's denoise_given_variance then filters the blend with v_out.
 
-Out of scope: moving spheres get no motion vectors (their blur is already in
-every frame's time average), and reflections and refractions are reprojected
-at their first-hit point; max_history bounds how long either can lag.
+Object motion (NumpyOps.temporal(motion=) / temporal_variance(motion=),
+rt_temporal_motion_device / rt_temporal_variance_motion_device;
+TemporalDisplay.edited).  After Renderer.move_spheres, set_transforms or
+move_quads the history describes the scene before the edit.  A pose
+(Renderer.pose_device) is a device snapshot of what those edits write;
+Renderer.motion_device gives per pixel a render.MOTION_DTYPE record: d, where
+the surface point under the pixel centre stood at the pose minus where it is,
+dn, the same for its unit normal, and trace's t / object / chain_object.
+
+ 9. with a motion plane, a pixel with |n|^2 >= 0.25 (a surface), a hit record
+    (object >= 0) and d, dn not all zero substitutes P_m = P + d for P in step
+    2 (v, den, x, y, r) and in step 3's plane test, n_m = n + dn for n in the
+    normal test, and n_m / |n_m| for n / |n| as the plane's normal.  What is
+    written is unchanged: geo = (n, z) is the current pose's.  Every other
+    pixel -- media, misses, unmoved surfaces -- takes steps 1 to 8 as they
+    are, so an all-zero plane gives the same bits; a non-finite d gives a NaN
+    x and no history.
+
+Out of scope: moving media (fog pixels keep the camera-only reprojection: a
+caller who moves a medium's transform still calls clear()); lighting that
+changes under a static pixel -- a moved shadow or reflection -- lags by at
+most max_history, as reflections and refractions, reprojected at their
+first-hit point, already do; motion-blurred spheres carry their blur in every
+frame's time average and move as their time-0 centre does.
 """
 import ctypes as C
 
@@ -185,26 +206,28 @@ class NumpyOps:
         return history_variance_bytes(frame)
 
     def temporal(self, frame_now, rgb, scale, tile_strata, strata_now, guides, guide_strata, frame_prev=None,
-                 history_prev=None, params=None):
+                 history_prev=None, params=None, motion=None):
         """-> (out [H, W, 3] float64, (col, geo) float32 [H, W, 4] each, margin [H, W]).
+        motion: rt_temporal_motion_device's plane, a render.MOTION_DTYPE array
+        [H, W] (step 9 of the module's definition); None: rt_temporal_device.
 
         margin: the smallest |lhs - rhs| / rhs over the surface and normal
         comparisons of the pixel's taps with w > 1e-6 (inf where it has none):
         a pixel with a tiny margin sits on a threshold, where another rounding
         of the same arithmetic may decide the other way."""
         return self._temporal(frame_now, rgb, scale, tile_strata, strata_now, guides, guide_strata, frame_prev,
-                              history_prev, params, None)
+                              history_prev, params, None, motion)
 
     def temporal_variance(self, frame_now, rgb, scale, tile_strata, strata_now, guides, guide_strata, variance_now,
-                          frame_prev=None, history_prev=None, params=None):
+                          frame_prev=None, history_prev=None, params=None, motion=None):
         """rt_temporal_variance_device -> (out, (col, geo, var), variance_out
         [H, W] float64, margin); history_prev is a (col, geo, var) triple, var
-        float32 [H, W].  out, col, geo and margin are temporal()'s."""
+        float32 [H, W].  out, col, geo and margin are temporal()'s; motion as there."""
         return self._temporal(frame_now, rgb, scale, tile_strata, strata_now, guides, guide_strata, frame_prev,
-                              history_prev, params, variance_now)
+                              history_prev, params, variance_now, motion)
 
     def _temporal(self, frame_now, rgb, scale, tile_strata, strata_now, guides, guide_strata, frame_prev,
-                  history_prev, params, variance_now):
+                  history_prev, params, variance_now, motion=None):
         """temporal() and, with variance_now, temporal_variance(): the colour is stated once."""
         if guide_strata < 1:
             raise ValueError("guide_strata must be >= 1")
@@ -232,9 +255,26 @@ class NumpyOps:
             prev = _cam(frame_prev)
             cp, p00p, dup, dvp = prev
             P = _centre_points(_cam(frame_now), ii, jj, z)
-            v = P - cp
+            nn = _dot(n, n)
+            plane = nn >= 0.25
+            nu = (1.0 / np.sqrt(np.where(plane, nn, 1.0)))[..., None] * n
+            n_t = n  # the normal the taps' normals are held to
+            if motion is not None:  # step 9: a moved surface pixel projects where its point stood
+                motion = np.asarray(motion)
+                if motion.shape != (H, W):
+                    raise ValueError("motion must be a MOTION_DTYPE array [H, W]")
+                d, dn = motion["d"].astype(np.float64), motion["dn"].astype(np.float64)
+                moved = plane & (motion["object"] >= 0) & ((d != 0).any(-1) | (dn != 0).any(-1))
+                with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+                    P = np.where(moved[..., None], P + d, P)  # selected, not added: P + 0 is not always P's bits
+                    n_t = np.where(moved[..., None], n + dn, n)
+                    nn_t = _dot(n_t, n_t)
+                    nu = np.where(moved[..., None], (1.0 / np.sqrt(np.where(moved, nn_t, 1.0)))[..., None] * n_t, nu)
             Np = np.cross(dup, dvp)
-            num, den = _dot(p00p - cp, Np), _dot(v, Np)
+            with np.errstate(invalid="ignore", over="ignore"):  # a non-finite d: a NaN x, no history
+                v = P - cp
+                num, den = _dot(p00p - cp, Np), _dot(v, Np)
+                r = np.sqrt(_dot(v, v))
             with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
                 q = cp + (num / den)[..., None] * v - p00p
                 x, y = _dot(q, dup) / _dot(dup, dup), _dot(q, dvp) / _dot(dvp, dvp)
@@ -242,10 +282,6 @@ class NumpyOps:
             x, y = np.where(possible, x, 0.0), np.where(possible, y, 0.0)
             fx, fy = np.floor(x), np.floor(y)
             x0, y0, wx, wy = fx.astype(np.int64), fy.astype(np.int64), x - fx, y - fy
-            r = np.sqrt(_dot(v, v))
-            nn = _dot(n, n)
-            plane = nn >= 0.25
-            nu = (1.0 / np.sqrt(np.where(plane, nn, 1.0)))[..., None] * n
             Wv, cnt, se = np.zeros((H, W)), np.zeros((H, W)), np.zeros((H, W, 3))
             for b in (0, 1):
                 for a in (0, 1):
@@ -258,8 +294,8 @@ class NumpyOps:
                     near = inside & (w > 1e-6)
                     with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
                         if sn is not None:
-                            dn = n - gq[..., :3]
-                            lhs = _dot(dn, dn)
+                            dq = n_t - gq[..., :3]
+                            lhs = _dot(dq, dq)
                             ok &= lhs <= sn * sn
                             margin = np.fmin(margin, np.where(near, np.abs(lhs - sn * sn) / (sn * sn), np.inf))
                         if sz is not None:
@@ -324,8 +360,10 @@ class HipOps:
             return t.empty((self.history_bytes(frame),), dtype=t.uint8, device=self.device)
 
     def temporal(self, frame_now, rgb, scale, tile_strata, strata_now, guides, guide_strata, frame_prev=None,
-                 history_prev=None, params=None, history_out=None, out=None):
-        """-> (out [H, W, 3] float64, history_out uint8), both CUDA tensors."""
+                 history_prev=None, params=None, history_out=None, out=None, motion=None):
+        """-> (out [H, W, 3] float64, history_out uint8), both CUDA tensors.
+        motion: a CUDA tensor holding motion_device's plane for this frame
+        (rt_temporal_motion_device); None: rt_temporal_device."""
         t = self.torch
         if history_out is None:
             history_out = self.history(frame_now)
@@ -334,6 +372,17 @@ class HipOps:
                 out = t.empty((frame_now.image_height, frame_now.image_width, 3), dtype=t.float64,
                               device=self.device)
         p = abi.temporal_params(params)
+        if motion is not None:
+            check(self.lib.rt_temporal_motion_device(
+                C.byref(frame_now), C.c_void_p(rgb.data_ptr()), C.c_double(scale),
+                C.c_void_p(tile_strata.data_ptr() if tile_strata is not None else 0), int(strata_now),
+                C.c_void_p(guides.data_ptr()), int(guide_strata),
+                C.byref(frame_prev) if frame_prev is not None else None,
+                C.c_void_p(history_prev.data_ptr() if history_prev is not None else 0),
+                C.c_void_p(motion.data_ptr()), C.byref(p) if p is not None else None,
+                C.c_void_p(history_out.data_ptr()), C.c_void_p(out.data_ptr()),
+                C.c_void_p(self.stream.cuda_stream)))
+            return out, history_out
         check(self.lib.rt_temporal_device(
             C.byref(frame_now), C.c_void_p(rgb.data_ptr()), C.c_double(scale),
             C.c_void_p(tile_strata.data_ptr() if tile_strata is not None else 0), int(strata_now),
@@ -357,8 +406,9 @@ class HipOps:
 
     def temporal_variance(self, frame_now, rgb, scale, tile_strata, strata_now, guides, guide_strata, variance_now,
                           frame_prev=None, history_prev=None, params=None, history_out=None, out=None,
-                          variance_out=None):
-        """rt_temporal_variance_device -> (out [H, W, 3] float64, history_out uint8, variance_out [H, W] float64)."""
+                          variance_out=None, motion=None):
+        """rt_temporal_variance_device -> (out [H, W, 3] float64, history_out uint8, variance_out [H, W] float64);
+        with `motion` (as for temporal) rt_temporal_variance_motion_device."""
         t = self.torch
         h, w = frame_now.image_height, frame_now.image_width
         if history_out is None:
@@ -369,6 +419,18 @@ class HipOps:
             if variance_out is None:
                 variance_out = t.empty((h, w), dtype=t.float64, device=self.device)
         p = abi.temporal_params(params)
+        if motion is not None:
+            check(self.lib.rt_temporal_variance_motion_device(
+                C.byref(frame_now), C.c_void_p(rgb.data_ptr()), C.c_double(scale),
+                C.c_void_p(tile_strata.data_ptr() if tile_strata is not None else 0), int(strata_now),
+                C.c_void_p(guides.data_ptr()), int(guide_strata),
+                C.byref(frame_prev) if frame_prev is not None else None,
+                C.c_void_p(history_prev.data_ptr() if history_prev is not None else 0),
+                C.c_void_p(motion.data_ptr()), C.c_void_p(variance_now.data_ptr()),
+                C.byref(p) if p is not None else None, C.c_void_p(history_out.data_ptr()),
+                C.c_void_p(out.data_ptr()), C.c_void_p(variance_out.data_ptr()),
+                C.c_void_p(self.stream.cuda_stream)))
+            return out, history_out, variance_out
         check(self.lib.rt_temporal_variance_device(
             C.byref(frame_now), C.c_void_p(rgb.data_ptr()), C.c_double(scale),
             C.c_void_p(tile_strata.data_ptr() if tile_strata is not None else 0), int(strata_now),
@@ -392,9 +454,15 @@ class TemporalDisplay:
     blend through rt_denoise_device (`denoise`: its rt_denoise_params).
     reset(frame) is the camera move: the last displayed frame's history and
     its rt_frame are committed, the wrapped renderer and the guides restart,
-    and the history is kept; a frame of another size drops it.  clear()
-    forgets the history (a scene change).  Two histories, the blend and
-    DenoisedDisplay's buffers are allocated once per frame size.
+    and the history is kept; a frame of another size drops it.  edited() is
+    the scene edit's counterpart (after Renderer.move_spheres, set_transforms
+    or move_quads): the history is committed in the same way and marked as
+    moved, and until the next camera-only reset() every frame reprojects along
+    the objects' motion as well (rt_motion_device once per pose, then
+    rt_temporal_motion_device).  clear() forgets the history (a change no
+    motion vector describes: a moved medium, another scene).  Two histories,
+    two poses, the motion plane, the blend and DenoisedDisplay's buffers are
+    allocated once per frame size.
 
         td = TemporalDisplay(progressive.for_renderer(R, frame, seed=5))
         pipe = progressive.DisplayPipeline(td, bytes_fn=td.bytes_into)
@@ -419,6 +487,45 @@ class TemporalDisplay:
         self._shape = (f.image_width, f.image_height)
         self.frame_prev = None   # the rt_frame hist[0] was taken at; None: no history
         self._shown = None       # the rt_frame hist[1] was written at by the last image()
+        self._allocate_motion()
+
+    # while the history is marked as moved and the caller's params leave these at 0: the set
+    # include/rt_api.h recommends for larger per-frame motion (the shipped 0.5 depth tolerance
+    # would let an uncovered floor pixel keep the sphere that stood on it)
+    MOVED_PARAMS = dict(max_history=32, sigma_depth=0.02, sigma_normal=0.35)
+
+    def _allocate_motion(self):
+        """The poses (once: they belong to the scene, not to the frame size) and the motion plane."""
+        t, f, R = self.torch, self.pr.frame, self.dd.renderer
+        with t.cuda.stream(self.stream):
+            if not hasattr(self, "pose"):  # [0]: the scene hist[0] shows, [1]: the scene as it stands
+                self.pose = [t.empty((R.pose_bytes(),), dtype=t.uint8, device=self.pr.acc.device) for _ in range(2)]
+                self._save_pose()
+            self.motion = t.empty((f.image_height * f.image_width * 64,), dtype=t.uint8, device=self.pr.acc.device)
+        self._moved = False         # hist[0] shows another pose of the scene than the current one
+        self._motion_ready = False  # self.motion holds pr.frame's plane against pose[0]
+
+    def _save_pose(self):
+        self.dd.renderer.pose_device(self.pose[1].data_ptr(), self.stream.cuda_stream)
+
+    def _motion_plane(self):
+        """The motion plane of the current frame while the history is marked as moved (computed once per pose), else None."""
+        if not (self._moved and self.has_history):
+            return None
+        if not self._motion_ready:
+            self.dd.renderer.motion_device(self.pr.frame, self.pose[0].data_ptr(), self.motion.data_ptr(),
+                                           self.stream.cuda_stream)
+            self._motion_ready = True
+        return self.motion
+
+    def _params_now(self, moved):
+        if not moved:
+            return self.params
+        p = abi.TemporalParams.from_buffer_copy(self.params) if self.params is not None else abi.TemporalParams()
+        for k, v in self.MOVED_PARAMS.items():
+            if getattr(p, k) == 0:
+                setattr(p, k, v)
+        return p
 
     # what DisplayPipeline reads of a renderer
     @property
@@ -457,10 +564,11 @@ class TemporalDisplay:
         """The blend alone ([H, W, 3] float64 CUDA tensor); writes the displayed frame's history."""
         dd, pr = self.dd, self.pr
         dd._catch_up()
+        motion = self._motion_plane()
         self.ops.temporal(pr.frame, pr.acc, 1.0 if self._adaptive else pr.scale,
                           pr.tile_strata if self._adaptive else None, self.samples_taken, dd.guides,
                           max(1, dd.guides_done), self.frame_prev, self.hist[0] if self.has_history else None,
-                          self.params, self.hist[1], self.blend)
+                          self._params_now(motion is not None), self.hist[1], self.blend, motion=motion)
         self._shown = abi.Frame.from_buffer_copy(pr.frame)
         return self.blend
 
@@ -481,20 +589,35 @@ class TemporalDisplay:
 
     def reset(self, frame=None):
         """Camera moved: commit the last displayed frame's history, restart the renderer and the guides."""
-        if self._shown is not None:
+        if self._shown is not None:  # the poses swap exactly when the histories do
             self.hist.reverse()
+            self.pose.reverse()
             self.frame_prev, self._shown = self._shown, None
+            self._save_pose()
+            self._moved = False  # the committed history shows the scene as it stands
+        self._motion_ready = False
         self.dd.reset(frame)
         if (self.pr.frame.image_width, self.pr.frame.image_height) != self._shape:
             self._allocate()
 
+    def edited(self):
+        """The scene was edited (Renderer.move_spheres, set_transforms, move_quads, or their
+        _device forms queued on any stream before this call): commit the last displayed frame's
+        history exactly as reset() does -- with nothing shown, nothing swaps -- save the
+        scene's new pose, restart the renderer and the guides, and mark the history as moved:
+        until the next camera-only reset() commits a history of the scene as it stands,
+        blended() reprojects along the objects' motion too, with MOVED_PARAMS where the
+        caller's params are 0.  A moved medium has no motion vectors: clear() after it."""
+        self.reset()
+        self._save_pose()  # reset() saved one only if it committed; the edit may have come since
+        self._moved = self.has_history
+
     def clear(self):
-        """Forget the history (the scene changed): the next frames start from the samples alone.
-        After Renderer.move_spheres the caller calls reset() and then clear():
-        the reprojection follows the camera only, it has no motion vectors, so
-        a history of the old scene would be blended onto moved objects (object
-        motion in the temporal displays is future work)."""
+        """Forget the history: the next frames start from the samples alone.  For a change
+        edited() cannot follow -- a medium's transform moved (fog pixels keep the camera-only
+        reprojection), another scene behind the same display -- after reset()."""
         self.frame_prev = self._shown = None
+        self._moved = self._motion_ready = False
 
 
 class TemporalVarianceDisplay(TemporalDisplay):
@@ -514,7 +637,8 @@ class TemporalVarianceDisplay(TemporalDisplay):
      3. with `filter`, rt_denoise_given_variance_device(blend, scale 1, no tile
         strata, v_out).
     `denoise`: the filter's rt_denoise_variance_params.  step, blended, bytes,
-    bytes_into, reset (the history swap), clear and has_history are
+    bytes_into, reset (the history swap), edited (object motion, through
+    rt_temporal_variance_motion_device), clear and has_history are
     TemporalDisplay's; a frame of another size drops the history.  variance()
     is the displayed frame's variance plane ([H, W] float64): the filter's
     final v, or v_out with filter off.  Every buffer is allocated once per
@@ -552,6 +676,7 @@ class TemporalVarianceDisplay(TemporalDisplay):
         self.frame_prev = None
         self._shown = None
         self._filtered = False
+        self._allocate_motion()
 
     def blended(self):
         """The blend alone; writes v_out and the displayed frame's variance history."""
@@ -562,9 +687,11 @@ class TemporalVarianceDisplay(TemporalDisplay):
         dd.ops.denoise_variance(pr.frame, pr.acc, scale, strata, dd.guides, g, pr.s1 if ad else None,
                                 pr.s2 if ad else None, pr.batch_strata if ad else 0, self._estimate, dd.workspace,
                                 dd.out, self.v_now)
+        motion = self._motion_plane()
         self.ops.temporal_variance(pr.frame, pr.acc, scale, strata, self.samples_taken, dd.guides, g, self.v_now,
-                                   self.frame_prev, self.hist[0] if self.has_history else None, self.params,
-                                   self.hist[1], self.blend, self.v_out)
+                                   self.frame_prev, self.hist[0] if self.has_history else None,
+                                   self._params_now(motion is not None), self.hist[1], self.blend, self.v_out,
+                                   motion=motion)
         self._shown = abi.Frame.from_buffer_copy(pr.frame)
         self._filtered = False
         return self.blend
