@@ -198,6 +198,69 @@ RT_HD RT_FI V3 unitv(V3 a) { // Vec3::normalize (Vec3.hpp:150-158)
   return unitv_2t(a);
 #endif
 }
+// ONB(n) (ONB.hpp:25-37) and the direction lc in it without their products with
+// an exact zero: the Lambertian-only flat instance's form (shade, RT_ONB_AXIS_MS).
+// The general form is  w = unitv(n), a = |w.x| > 0.9 ? (0,1,0) : (1,0,0),
+// ov = unitv(cross(w, a)), ou = cross(w, ov), gd = (lc.x ou + lc.y ov) + lc.z w.
+// a has two exact zeros, so with q = w.y, p = w.x (a = x) the cross product is
+// (+-0, w.z, -q): its squared length (0 + w.z^2) + q^2, ov = (+-0, m1, -m2) with
+// m1 = w.z s, m2 = q s, and ou = (-(q m2) - (w.z m1), p m2, p m1); the build has
+// no fast-math, so the general form issues every one of those products and sums
+// with +-0.  For a = y the same holds with x and y exchanged and ov negated:
+// exchange w.x and w.y going in, negate lc.y, exchange gd.x and gd.y coming out
+// (f is the same value with either operand order; negation is exact).
+// Returns whether the lane may take w and gd from here: both unit vectors come
+// from unitv's normal branch with finite lengths, so every operand is finite,
+// every dropped term is an exact +-0, and w and gd equal the general form's as
+// values.  Bits can differ only in the sign of a zero result where a dropped
+// +-0 was the only signed term.  Nobody reads that sign: no reciprocal of a
+// direction component is formed in the flat world (quad_t_aa rejects
+// |denom| < 1e-8), len2 and the squares are >= +0, every compare has
+// -0 == +0, and floor(-0) converts to 0.  A lane that gets false (a zero, tiny,
+// NaN or infinite normal) runs the general form: its (1,0,0) fallbacks and NaN
+// masks live there only.  Event by event against the general form:
+// tests/test_onb_axis.py; on gfx950: tests/test_onb_axis_gpu.py.
+// sqrt_n and rcp_n here go without their class selects (sqrt_pos, rcp_fin): for
+// the operands those selects serve -- a zero or infinite squared length, an
+// infinite length -- the device's iterations give NaN and the host's forms 0 or
+// inf, and the lane is refused either way.
+RT_HD RT_FI double sqrt_pos(double x) { // sqrt_n's bits for a finite x >= 2^-767
+#if defined(__HIP_DEVICE_COMPILE__)
+  double h;
+  return sqrt_rsq(x, __builtin_amdgcn_rsq(x), h);
+#else
+  return sqrt(x);
+#endif
+}
+RT_HD RT_FI double rcp_fin(double x) { // rcp_n's bits for a finite x in [2^-600, 2^600]
+#if defined(__HIP_DEVICE_COMPILE__)
+  const double y0 = __builtin_amdgcn_rcp(x);
+  double e = fma(-x, y0, 1.0);
+  const double y1 = fma(y0, e, y0);
+  e = fma(-x, y1, 1.0);
+  const double y2 = fma(y1, e, y1);
+  const double r = fma(-x, y2, 1.0);
+  return fma(r, y2, y2);
+#else
+  return 1.0 / x;
+#endif
+}
+RT_HD RT_FI bool onb_axis_gd(V3 n, V3 lc, V3 &w, V3 &gd) {
+  const double l = sqrt_pos(len2(n));
+  const double s0 = rcp_fin(l);
+  w = v3(n.x * s0, n.y * s0, n.z * s0);
+  const bool big = fabs(w.x) > 0.9;
+  const double q = big ? w.x : w.y, p = big ? w.y : w.x;
+  const double l2 = sqrt_pos(w.z * w.z + q * q);
+  const double s = rcp_fin(l2);
+  const double m1 = w.z * s, m2 = q * s;
+  const double f = -(q * m2) - (w.z * m1);
+  const double ly = big ? -lc.y : lc.y;
+  const double gp = lc.x * f + lc.z * p;
+  const double gq = (lc.x * (p * m2) + ly * m1) + lc.z * q;
+  gd = v3(big ? gq : gp, big ? gp : gq, (lc.x * (p * m1) + ly * (-m2)) + lc.z * w.z);
+  return l > 1e-8 && l < kInf && l2 > 1e-8 && l2 < kInf;
+}
 
 struct Ray {
   V3 o, d;
@@ -2238,6 +2301,18 @@ RT_HD RT_FI bool advance(PathState &ps, const DCamera &C) {
 // Not the BVH instances: their small far spheres round |oc|^2 - rr so that a
 // third of the primary hits fail the guard, and a wave would run both forms.
 #define RT_LAMBERT_ALBEDO_F(F) ((F) == F_FLAT)
+// The Lambertian-only flat instance builds its basis and direction without the
+// products with exact zeros (onb_axis_gd); make EXTRA=-DRT_ONB_AXIS=0 builds
+// the general form there too (the parent's text, for A/B runs).  The general
+// flat instance keeps the general form: its text is unchanged, and
+// tests/test_onb_axis_gpu.py compares the two instances' frames.  Measured (profiles/onb_*,
+// DESIGN.md section 9): 260 -> 230 VALU per pass, C2 SQ_INSTS_VALU -4.6 %,
+// GRBM_GUI_ACTIVE -3.1 %, frames bit-equal; kernel time -1.5 to -3.3 % on the
+// means of five-round sets whose ranges still touch.
+#ifndef RT_ONB_AXIS
+#define RT_ONB_AXIS 1
+#endif
+#define RT_ONB_AXIS_MS(MS) (RT_ONB_AXIS && (MS) == M_DIFFUSE)
 template <bool STATS, unsigned F, MatSet MS = M_ANY>
 RT_HD RT_FI bool shade(const DScene &S, const DCamera &C, PathState &ps, const Key &key,
                        const Hit &h, Counters &cnt) {
@@ -2367,13 +2442,39 @@ RT_HD RT_FI bool shade(const DScene &S, const DCamera &C, PathState &ps, const K
     }
     att = tex_value<F, MS>(S, M.tex, h.p);
   }
-  V3 w = kMerge ? u1 : unitv(h.n); // ONB(n), ONB.hpp:25-37
-  V3 a = (fabs(w.x) > 0.9) ? v3(0, 1, 0) : v3(1, 0, 0);
-  V3 ov = unitv(cross(w, a));
-  V3 ou = cross(w, ov);
+  // kAxis: the basis and the direction without their exact zeros (onb_axis_gd)
+  constexpr bool kAxis = RT_ONB_AXIS_MS(MS);
+  V3 w, gd;
+  V3 ov{}, ou{};
+  if constexpr (kAxis) {
+    double sp, cp; // random_cosine_direction, Vec3Utility.hpp:94-103
+    sincos_2pi<RT_KCONST_MODE(F)>(d0, sp, cp);
+    const double sr = sqrt_n(d1);
+    const V3 lc = v3(cp * sr, sp * sr, sqrt_pos(1 - d1)); // 1 - d1 in [2^-32, 1]: no zero to select
+    const bool fast = onb_axis_gd(h.n, lc, w, gd);
+    // The general form, for the lanes the reduced one refuses: a branch of the
+    // whole wave, so that none of its operations is speculated into the path
+    // that every wave runs (a per-lane else put the general gd there).
+    if (!wave_none(!fast)) {
+#if defined(__HIP_DEVICE_COMPILE__)
+      asm volatile("");
+#endif
+      if (!fast) {
+        w = unitv(h.n);
+        const V3 a = (fabs(w.x) > 0.9) ? v3(0, 1, 0) : v3(1, 0, 0);
+        ov = unitv(cross(w, a));
+        ou = cross(w, ov);
+        gd = ((lc.x * ou) + (lc.y * ov)) + (lc.z * w);
+      }
+    }
+  } else {
+    w = kMerge ? u1 : unitv(h.n); // ONB(n), ONB.hpp:25-37
+    V3 a = (fabs(w.x) > 0.9) ? v3(0, 1, 0) : v3(1, 0, 0);
+    ov = unitv(cross(w, a));
+    ou = cross(w, ov);
+  }
   bool have_lights = false;
   if constexpr ((F & F_LIGHTS) != 0) have_lights = S.n_lights > 0;
-  V3 gd;
   bool from_light = false;
   // one sincos(2 pi a) for whichever of the light sample (a sphere light's
   // azimuth, a = d0), the cosine direction (a = d0) and the isotropic
@@ -2395,7 +2496,7 @@ RT_HD RT_FI bool shade(const DScene &S, const DCamera &C, PathState &ps, const K
       if (STATS && wave_once()) cnt.clights += clk() - t0;
     }
   }
-  if (!from_light) {
+  if (!kAxis && !from_light) {
     if (kSc) {
       if (lamb) { // random_cosine_direction, Vec3Utility.hpp:94-103
         double sr = sqrt_n(d1);
